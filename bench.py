@@ -1,6 +1,7 @@
 """bench.py — env-steps/sec of the batched bsuite step() path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload deep_sea|catch|...|sweep] [--lanes B] [--weak]
+                  [--full] [--dump-outputs DIR]
 
 One "step" = one env.step(actions) call on every lane of the batch (auto-reset calls included,
 they are real API calls: bsuite/environments/base.py:61-62).  Default workload is BASELINE.json
@@ -10,11 +11,17 @@ Every TimeStep field is materialised in HBM on every step (dense contract).  Bef
 lanes are put at staggered episode phases, so that every timed call carries the steady-state mix of
 FIRST / MID / LAST lanes whatever K is.
 
-The default line also carries the other BASELINE configs as sub-records under "also" — catch/0
-(configs[2]) first, then cartpole/0 and mountain_car/0 (configs[3]; eager step(), a HIP graph of 16
-step() launches, the fused rollout(T=16)) and the 468-id sweep (configs[4]) — in a compact form: 5
-significant digits, short codes instead of prose (legend: DESIGN.md §6), so that the whole line stays
-well under 8000 characters.
+A plain run measures the headline workload only: set-up, W warm-up steps, K timed steps, one line
+(`ms_per_step` = wall milliseconds of one timed step).  `--full` adds everything else the line can
+carry: the other BASELINE configs as sub-records under "also" — catch/0 (configs[2]) first, then
+cartpole/0 and mountain_car/0 (configs[3]; eager step(), a HIP graph of 16 step() launches, the fused
+rollout(T=16)) and the 468-id sweep (configs[4]) — in a compact form: 5 significant digits, short codes
+instead of prose (legend: DESIGN.md §6), so that the whole line stays well under 8000 characters; the
+box's fill and copy ceilings, the host's cost of one step, the live CPU baseline, and the sweep's other
+two schedules.
+
+`--dump-outputs DIR` writes the TimeStep the last timed step returned (rank 0's lanes) as float32
+`DIR/<field>.npy`, 64 MB at most (dump_outputs); inputs are seeded, so two builds compare output for output.
 
 Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL); lanes shard with no
 data-path collective; the only collective is the end-of-rollout all-gather of per-rank summaries.
@@ -108,6 +115,39 @@ def pmc_valu(workload, mode, lanes):
   if d is None or lanes != d.get('lanes', 1 << 20):
     return None
   return dict(insts=d['per_launch']['SQ_INSTS_VALU'], busy=d['per_launch'].get('valu_busy_frac'), src=src)
+
+
+DUMP_BYTES = 60 << 20        # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, fields, budget=DUMP_BYTES):
+  """--dump-outputs: writes each array of `fields` (name -> tensor, leading dimension = lanes) as float32
+  `out_dir/<name>.npy`, smallest first.  An array that does not fit its share of what is left of `budget` is cut
+  to a fixed, seeded sample of its rows (the same rows on every run of the same shape), whose indices are written
+  as float64 `out_dir/<name>_rows.npy`."""
+  import numpy as np
+  import torch
+  os.makedirs(out_dir, exist_ok=True)
+  left = budget
+  order = sorted(fields, key=lambda k: fields[k].numel())
+  for i, name in enumerate(order):
+    x = fields[name].detach()
+    rows = x.shape[0]
+    row_bytes = 4 * (x[0].numel() if rows else 0)
+    share = left // (len(order) - i)
+    if rows * row_bytes > share:
+      n = max(1, share // (row_bytes + 8))
+      pick = np.sort(np.random.default_rng(0).choice(rows, size=min(n, rows), replace=False))
+      np.save(os.path.join(out_dir, f'{name}_rows.npy'), pick.astype(np.float64))
+      x = x.index_select(0, torch.from_numpy(pick).to(x.device))
+      left -= 8 * len(pick)
+    a = x.to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, f'{name}.npy'), a)
+    left -= a.nbytes
+
+
+def _timestep_fields(ts):
+  return {'step_type': ts.step_type, 'reward': ts.reward, 'discount': ts.discount, 'observation': ts.observation}
 
 
 def sig(x, n=5):
@@ -412,10 +452,10 @@ class Rank:
 
   # -------------------------------------------------------------------------------------------
   def measure(self, workload, lanes, steps, warmup, mode='eager', chunk=0, observation_mode='dense',
-              logging=False, stagger=True):
+              logging=False, stagger=True, dump=None):
     """Times `steps` step() calls of `workload` on `lanes` lanes per rank.  mode: 'eager' (one
     entry-point call per step), 'graph' (HIP graph of `chunk` step() launches), 'rollout' (fused
-    rollout(actions[chunk, B]))."""
+    rollout(actions[chunk, B])).  `dump`: directory for dump_outputs() of the last timed step (rank 0)."""
     torch, args = self.torch, self.args
     bsuite_id, family, okw, obs_numel, state_bytes, period = WORKLOADS[workload]
     B = lanes
@@ -441,6 +481,7 @@ class Rank:
     else:
       env.step(actions[0])
 
+    last = [None]                                 # the TimeStep of the latest step, as its caller receives it
     if mode == 'graph':
       assert steps % chunk == 0 and warmup % chunk == 0, '--steps/--warmup must be multiples of --graph'
       side = torch.cuda.Stream(device=self.dev)
@@ -450,7 +491,7 @@ class Rank:
         with torch.cuda.graph(graph, stream=side):
           with _raw(env).step_counter_deferred():        # one call-counter bump per replay, not per step
             for t in range(chunk):
-              env.step(actions[t])
+              last[0] = env.step(actions[t])             # (a replay rewrites these buffers)
       torch.cuda.current_stream(self.dev).wait_stream(side)
 
       def run(n_steps):
@@ -461,17 +502,22 @@ class Rank:
 
       def run(n_steps):
         for _ in range(n_steps // chunk):
-          env.rollout(actions[:chunk])
+          last[0] = env.rollout(actions[:chunk])
     else:
       def run(n_steps):
         for t in range(n_steps):
-          env.step(actions[t % n_act])
+          last[0] = env.step(actions[t % n_act])
 
     run(warmup)                                   # (untimed; the LAST / FIRST counts below are those of the timed steps only)
     torch.cuda.synchronize(self.dev)
     before = _raw(env).episode_counters().clone()
     wall, kernel_ms = self.timed(run, steps, 0)
     ended = (_raw(env).episode_counters() - before).to(torch.float64)
+    if dump and self.rank == 0:
+      fields = _timestep_fields(last[0])
+      if mode == 'rollout':                       # [T, B, ...]: the last of the call's T steps
+        fields = {k: v[-1] for k, v in fields.items()}
+      dump_outputs(dump, fields)
 
     # end-of-rollout summary: the only collective on the path (RCCL all-gather over xGMI)
     from bsuite_amd import distributed as bdist
@@ -610,18 +656,20 @@ class Rank:
       self._host_step_us = dt / calls * 1e6
     return self._host_step_us
 
-  def roofline(self, r, full=False):
+  def roofline(self, r, full=False, ceiling=False):
     """HBM roofline of a record: algorithmic bytes per launch / launch time by HIP events.  Fused
     rollouts of the physics families also carry the VALU-issue roofline (`valu`: wave-instructions of the committed
     SQ pass / launch time against one wave64 instruction per 2 cycles and SIMD): their state stays in registers for
     T steps, and neither ceiling is close — the record's `bound` is the nearer one (DESIGN §3.3 has the ablations:
-    cartpole 7.1 us of arithmetic + 5.1 us of stores at the fill rate, 10.6-11 us measured)."""
+    cartpole 7.1 us of arithmetic + 5.1 us of stores at the fill rate, 10.6-11 us measured).  `ceiling` adds the box's
+    measured fill rate (store_ceiling: a run of its own, --full only)."""
     out = {'bound': 'hbm', 'achieved': r['achieved'], 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
            'frac': r['achieved'] / HBM_PEAK_GBPS, 'traffic': r['traffic']}
     if full:
-      ceiling = self.store_ceiling()
-      out.update(traffic_src=r['traffic_src'], alg_bytes=int(round(r['bytes_per_step'] * r['lanes'])), kernel_ms=r['kernel_ms'],
-                 box_fill_GBps=ceiling, frac_of_box_fill=r['achieved'] / ceiling)
+      out.update(traffic_src=r['traffic_src'], alg_bytes=int(round(r['bytes_per_step'] * r['lanes'])), kernel_ms=r['kernel_ms'])
+    if ceiling:
+      fill = self.store_ceiling()
+      out.update(box_fill_GBps=fill, frac_of_box_fill=r['achieved'] / fill)
     if r['mode'] == 'rollout' and r['family'] in ('cartpole', 'mountain_car'):
       v = pmc_valu(r['workload'], f"rollout{r['chunk']}", r['lanes'])
       if v is not None:
@@ -666,16 +714,19 @@ class Rank:
     return out
 
   # -------------------------------------------------------------------------------------------
-  def measure_sweep(self, lanes, steps, warmup, ring=16):
+  def measure_sweep(self, lanes, steps, warmup, ring=16, dump=None):
     """BASELINE config 5: all 468 bsuite_ids as lane segments (`lanes` in total, split evenly per id, whole
     segments bin-packed over the ranks), the whole sweep as ONE launch group.  Random actions over time: every
     segment reads row (sweep step mod `ring`) of a pre-generated [ring, lanes] action ring on the device
-    (bsx_call_t.action_ring; SURVEY §8d actions [T,B]).  Two schedules are timed on the same batch:
+    (bsx_call_t.action_ring; SURVEY §8d actions [T,B]).  With --full two schedules are timed on the same batch
+    (a plain run times the first only):
       closed-loop (the record's `value`): two launches per sweep step — phase 0 advances every lane and bumps the
         call counter, phase 1 is the observation store stream; the TimeSteps of step s are complete before the
         actions of step s+1 are needed;
       open-loop (`pipelined`): one launch per step — the store stream of step s beside the lane advance of step
-        s+1 — valid because the actions do not depend on the observations; not reachable by a closed-loop agent."""
+        s+1 — valid because the actions do not depend on the observations; not reachable by a closed-loop agent.
+    `dump`: directory for dump_outputs() of the closed-loop schedule's last timed step, the rank's segments in
+    order, each field concatenated over them (observations flattened)."""
     import tempfile
     import numpy as np
     torch = self.torch
@@ -691,19 +742,28 @@ class Rank:
     acts = batch.random_actions(seed=1, ring=ring)   # keyed by segment: independent of the rank assignment
     local_bytes = float(sum(l * sb.bytes_per_step(int(np.prod(e.observation_spec().shape)))
                             for e, (_, _, l) in zip(batch.envs, batch.segments)))
+    # `value`: the closed-loop schedule step_grouped() runs by default (sweep_batch.DEFAULT_SPLIT); the other closed-loop
+    # cut of the same two launches beside it
+    main, other = ('split', 'closed') if sb.DEFAULT_SPLIT else ('closed', 'split')
     timed = {}
     only = getattr(self.args, 'sweep_schedule', 'all')            # (profiling passes time ONE schedule: its kernels' dispatches then are its own)
+    if only == 'all' and not getattr(self.args, 'full', True):
+      only = main                                                  # a plain run: the headline's schedule alone
     for name, pipelined in (('closed', False), ('split', False), ('pipelined', True)):
       if only not in ('all', name):
         continue
       batch.prepare_groups(acts, pipelined=pipelined, rows_in_stream=(None if self.args.row_path == 'auto' else self.args.row_path == 'on'),
                            split=(name == 'split'))
+      last = [None]
 
       def run(n):
         for _ in range(n):
-          batch.step_grouped()
+          last[0] = batch.step_grouped()
 
       timed[name] = self.timed(run, steps, warmup)
+      if dump and self.rank == 0 and name == (main if only == 'all' else only):
+        dump_outputs(dump, {k: torch.cat([f[k].reshape(-1) for f in map(_timestep_fields, last[0])])
+                            for k in ('step_type', 'reward', 'discount', 'observation')})
       batch.release_groups()
     # the only collective: all-gather of the per-rank summaries (here: bytes + lanes + episode counters)
     summ = batch.summary()
@@ -718,9 +778,6 @@ class Rank:
               'traffic': traffic}
 
     tr = {k: (pmc_traffic(k, int(total_lanes))[0] if self.world == 1 else None) for k in ('sweep_closed', 'sweep_split', 'sweep_pipelined')}
-    # `value`: the closed-loop schedule step_grouped() runs by default (sweep_batch.DEFAULT_SPLIT); the other closed-loop
-    # cut of the same two launches beside it
-    main, other = ('split', 'closed') if sb.DEFAULT_SPLIT else ('closed', 'split')
     modes = {'closed': 'closed-loop, 2 launches/step: phase 0 | store stream',
              'split': 'closed-loop, 2 launches/step: advance of the stream families | store stream + small families'}
     if only != 'all':
@@ -728,7 +785,8 @@ class Rank:
       rec = {'value': total_lanes * steps / wall, 'ms_per_step': wall / steps * 1e3, 'steps': steps,
              'mode': modes.get(only, 'open-loop, 1 launch/step'), 'global_lanes': int(total_lanes),
              'segments_per_rank': [int(x) for x in g[:, 2].tolist()], 'action_ring': ring, 'alg_bytes_busiest_rank': max_rank_bytes,
-             'roofline': roof(step_ms, tr['sweep_' + only]), 'pipelined': {'open_loop': True}, 'episodes_finished': float(g[:, 3].sum())}
+             'roofline': roof(step_ms, tr['sweep_' + only]), 'episodes_finished': float(g[:, 3].sum()),
+             **({'pipelined': {'open_loop': True}} if only == 'pipelined' else {})}
       del batch, acts
       torch.cuda.empty_cache()
       return rec
@@ -763,7 +821,7 @@ class Rank:
       from bsuite_amd.environments import base as _base
       _base.Environment.row_path_min_bytes = 0 if args.row_path == 'on' else None
     if args.workload == 'sweep':
-      rec = self.measure_sweep(args.lanes, args.steps, args.warmup)
+      rec = self.measure_sweep(args.lanes, args.steps, args.warmup, dump=args.dump_outputs)
       if self.rank == 0:
         line = {'metric': 'env-steps/sec', 'value': rec['value'], 'unit': 'env-steps/s', 'n_gpus': world,
                 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': rec['ms_per_step'],
@@ -772,8 +830,8 @@ class Rank:
                 'config': {'workload': 'sweep.SWEEP: 468 bsuite_ids as lane segments, random-action ring, dense TimeStep',
                            'global_lanes': rec['global_lanes'], 'segments_per_rank': rec['segments_per_rank'],
                            'sharding': f'whole segments bin-packed over {world} rank(s) by lanes x bytes/step'},
-                'roofline': rec['roofline'], 'launch': rec['mode'], 'pipelined': rec['pipelined'],
-                **{k: rec[k] for k in ('closed', 'split') if k in rec},
+                'roofline': rec['roofline'], 'launch': rec['mode'],
+                **{k: rec[k] for k in ('pipelined', 'closed', 'split') if k in rec},
                 'episodes_finished': rec['episodes_finished']}
         print(json.dumps(sig(line)), flush=True)
       return
@@ -787,9 +845,10 @@ class Rank:
       lanes //= world
 
     mode, chunk = ('graph', args.graph) if args.graph else ('rollout', args.rollout) if args.rollout else ('eager', 0)
-    m = self.measure(args.workload, lanes, args.steps, args.warmup, mode, chunk, args.observation_mode, args.logging)
+    m = self.measure(args.workload, lanes, args.steps, args.warmup, mode, chunk, args.observation_mode, args.logging,
+                     dump=args.dump_outputs)
     also = {}
-    headline = (args.workload == 'deep_sea' and mode == 'eager' and args.observation_mode == 'dense'
+    headline = (args.full and args.workload == 'deep_sea' and mode == 'eager' and args.observation_mode == 'dense'
                 and not args.logging and not args.no_also)
     if headline:
       # The sub-records are extras of the line, not the contract's K timed steps: their kernels run 10-45 us,
@@ -853,7 +912,7 @@ class Rank:
                      'lanes_per_gpu': B, 'global_lanes': B * world, 'bytes_per_env_step': m['bytes_per_step'],
                      **({'pinned_cores_per_rank': self.pinned_cores} if world > 1 else {}),
                      'episode_phases': 'lock-step' if args.no_stagger else 'staggered'},
-          'roofline': self.roofline(m, full=True),
+          'roofline': self.roofline(m, full=True, ceiling=args.full),
       }
       if also:
         line['also'] = also
@@ -862,7 +921,7 @@ class Rank:
       if world == 1 and headline:
         line['host'] = {'step_us': self.host_step_us(), 'box_copy_GBps': self.copy_ceiling()}
       line.update(episodes_finished=m['episodes_finished'], bsuite_info_sums=m['info_sums'], timed_mix=m['timed_mix'])
-      if world == 1 and not args.no_cpu_baseline:
+      if world == 1 and args.full and not args.no_cpu_baseline:
         line['cpu_baseline'] = cpu_baseline(m['bsuite_id'], m['family'], m['okw'], m['num_actions'])
       text = json.dumps(sig(line))
       if len(text) >= 7800:                 # the driver keeps an 8000-character tail: never let the line outgrow it
@@ -886,10 +945,15 @@ def main():
                   help='GLOBAL lane count (BASELINE.json: batch = 2^20), split evenly over the ranks (strong scaling)')
   ap.add_argument('--weak', action='store_true', help='weak scaling: --lanes per GPU')
   ap.add_argument('--strong', action='store_true', help='(the default; kept for older command lines)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure everything beside the headline: the other configs under "also", the box\'s fill / copy '
+                       'ceilings and host step cost, the live CPU baseline, the sweep\'s other schedules')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the TimeStep of the last timed step as float32 DIR/<field>.npy (at most 64 MB; dump_outputs)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--sustained', type=float, default=5.0,
                   help='seconds of eager deep_sea steps in the `also["deep_sea/10 sustained"]` record (catch: 0.4 x)')
-  ap.add_argument('--no-also', action='store_true', help='only the main workload (no catch / cartpole / sweep sub-records)')
+  ap.add_argument('--no-also', action='store_true', help='with --full: only the main workload (no catch / cartpole / sweep sub-records)')
   ap.add_argument('--no-stagger', action='store_true', help='start all lanes in lock-step (fresh lanes, first call = reset)')
   ap.add_argument('--logging', action='store_true',
                   help='wrap the environment in the batched Logging wrapper (bookkeeping fused into the kernels)')

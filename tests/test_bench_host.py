@@ -95,3 +95,28 @@ def test_committed_pmc_passes_feed_the_roofline_fields():
     assert v is not None and v['insts'] > 1e7 and 0.2 < v['busy'] < 1.0, (w, v)
   # VALU issue peak: 256 CUs x 4 SIMDs, one wave64 instruction per 2 cycles at 2.4 GHz
   assert abs(bench.VALU_PEAK_GINSTR - 1228.8) < 1e-9
+
+
+def test_dump_outputs_fit_the_budget_with_a_fixed_sample(tmp_path):
+  """--dump-outputs: float32 files, whole where they fit, else the same seeded rows on every run, under the budget."""
+  g = torch.Generator().manual_seed(3)
+  B = 4096
+  fields = {'step_type': torch.randint(0, 3, (B,), generator=g).to(torch.int8), 'reward': torch.rand(B, generator=g),
+            'discount': torch.ones(B), 'observation': torch.rand((B, 30, 30), generator=g)}
+  budget = 1 << 20
+  for d in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / d), fields, budget=budget)
+  files = sorted(os.listdir(tmp_path / 'a'))
+  assert files == ['discount.npy', 'observation.npy', 'observation_rows.npy', 'reward.npy', 'step_type.npy']
+  assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) < budget + 1024
+  for f in files:
+    a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+    assert a.dtype == (np.float64 if f.endswith('_rows.npy') else np.float32) and np.array_equal(a, b), f
+  for k in ('step_type', 'reward', 'discount'):
+    assert np.array_equal(np.load(tmp_path / 'a' / f'{k}.npy'), fields[k].float().numpy()), k
+  rows = np.load(tmp_path / 'a' / 'observation_rows.npy').astype(np.int64)
+  assert 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+  assert np.array_equal(np.load(tmp_path / 'a' / 'observation.npy'), fields['observation'].numpy()[rows])
+  bench.dump_outputs(str(tmp_path / 'whole'), fields)                 # the default budget holds all of it
+  assert not os.path.exists(tmp_path / 'whole' / 'observation_rows.npy')
+  assert np.array_equal(np.load(tmp_path / 'whole' / 'observation.npy'), fields['observation'].numpy())

@@ -57,7 +57,7 @@ def test_two_self_launched_ranks_reproduce_one_rank(workload):
 
 @pytest.mark.timeout(900)
 def test_default_line_two_ranks_is_strong_with_weak_and_sweep_records():
-  two = _bench('--gpus', '2', '--lanes', '8192', '--steps', '8', '--warmup', '4', ranks_on_one_gpu=True)
+  two = _bench('--gpus', '2', '--lanes', '8192', '--steps', '8', '--warmup', '4', '--full', ranks_on_one_gpu=True)
   assert two['n_gpus'] == 2 and two['config']['workload'].startswith('deep_sea/10')
   assert two['scaling'] == 'strong' and two['config']['lanes_per_gpu'] == 4096 and two['config']['global_lanes'] == 8192
   assert two['roofline']['alg_bytes'] == 3621 * 4096
@@ -67,7 +67,7 @@ def test_default_line_two_ranks_is_strong_with_weak_and_sweep_records():
   sweep = also['sweep']
   assert sum(sweep['segments_per_rank']) == 468 and min(sweep['segments_per_rank']) > 0
   assert sweep['global_lanes'] == 8192 and sweep['action_ring'] == 16 and sweep['pipelined']['open_loop'] is True
-  one = _bench('--gpus', '1', '--workload', 'sweep', '--lanes', '8192', '--steps', '100', '--warmup', '20')   # the sub-record's K / W
+  one = _bench('--gpus', '1', '--workload', 'sweep', '--lanes', '8192', '--steps', '100', '--warmup', '20', '--full')   # the sub-record's K / W
   assert one['episodes_finished'] == sweep['episodes_finished'] > 0
 
 
@@ -77,7 +77,7 @@ def test_default_line_fits_the_drivers_tail():
   with its roofline, the live cpu_baseline — must fit, catch/0 first among the sub-records."""
   env = dict(os.environ)
   env.pop('WORLD_SIZE', None)
-  p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--lanes', '65536', '--steps', '8', '--warmup', '4'],
+  p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--lanes', '65536', '--steps', '8', '--warmup', '4', '--full'],
                      env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=800)
   assert p.returncode == 0, p.stderr[-3000:]
   text = [l for l in p.stdout.splitlines() if l.startswith('{')][0]
@@ -106,7 +106,7 @@ def test_eight_self_launched_ranks_rehearsal():
   env.pop('RANK', None)
   env.update(BSX_BENCH_BACKEND='gloo', BSX_BENCH_SINGLE_DEVICE='1')
   p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--gpus', '8', '--lanes', '65536',
-                      '--steps', '8', '--warmup', '4'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1400)
+                      '--steps', '8', '--warmup', '4', '--full'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1400)
   assert p.returncode == 0, p.stderr[-3000:]
   lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
   assert len(lines) == 1 and len(lines[0]) < 7800, (len(lines), [len(l) for l in lines])
@@ -122,7 +122,7 @@ def test_eight_self_launched_ranks_rehearsal():
   one = _bench('--gpus', '1', '--lanes', '65536', '--steps', '8', '--warmup', '4', '--no-also')
   assert one['episodes_finished'] == eight['episodes_finished'] > 0
   assert one['bsuite_info_sums'] == eight['bsuite_info_sums'] and one['timed_mix'] == eight['timed_mix']
-  one_sweep = _bench('--gpus', '1', '--workload', 'sweep', '--lanes', '65536', '--steps', '100', '--warmup', '20')
+  one_sweep = _bench('--gpus', '1', '--workload', 'sweep', '--lanes', '65536', '--steps', '100', '--warmup', '20', '--full')
   assert one_sweep['episodes_finished'] == sweep['episodes_finished'] > 0
 
 

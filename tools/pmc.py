@@ -123,6 +123,8 @@ def main():
   bench_args = sys.argv[sep + 1:]
   if args.script:
     SCRIPT[0] = os.path.abspath(args.script)
+  elif '--full' not in bench_args:
+    bench_args = ['--full'] + bench_args        # the WRITE_SIZE calibration needs the fill kernel: bench.py runs it with --full only
   last = args.last or int(bench_args[bench_args.index('--steps') + 1])
   doc = dict(name=args.name, lanes=args.lanes, last_dispatches_per_kernel=last,
              command='rocprofv3 --pmc <one group per run> --kernel-trace --output-format csv -- python bench.py ' + ' '.join(bench_args)

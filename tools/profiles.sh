@@ -11,7 +11,7 @@ A="--no-cpu-baseline --no-also"
 if [ "$mode" != quick ] && [ -z "${SKIP_PYTEST:-}" ]; then
   ( time timeout 1700 python -m pytest tests -m gpu -q --durations=8 ) > $out/pytest_gpu.log 2>&1; tail -3 $out/pytest_gpu.log
 fi
-timeout 400 python bench.py > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json
+timeout 400 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; wc -c $out/bench_default.json
 # the headline under rocprofv3: kernel averages over the timed launches + the bench line of the same run
 timeout 400 python tools/kernel_stats.py $out/bench_headline_kernel_stats.csv -- --steps 200 --warmup 20 $A > /dev/null 2>$out/kernel_stats.err
 timeout 400 python tools/kernel_stats.py $out/bench_catch_kernel_stats.csv -- --workload catch --steps 200 --warmup 20 $A > /dev/null 2>>$out/kernel_stats.err
@@ -71,9 +71,9 @@ if [ "$mode" != quick ]; then
 import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-18s eager  %.3e env-steps/s  %.2f us/step  %.0f GB/s  frac %.3f' % ('$w', d['value'], r['kernel_ms']*1e3, r['achieved'], r['frac']))"
   done > $out/bench_all_workloads_eager.log
   timeout 900 python tools/strong_scaling_proxy.py $out/strong_scaling_proxy.json > $out/strong_scaling_proxy.log 2>&1
-  BSX_BENCH_BACKEND=gloo BSX_BENCH_SINGLE_DEVICE=1 timeout 400 python bench.py --gpus 2 --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_2ranks_on_one_gpu_gloo.json
+  BSX_BENCH_BACKEND=gloo BSX_BENCH_SINGLE_DEVICE=1 timeout 400 python bench.py --gpus 2 --full --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_2ranks_on_one_gpu_gloo.json
   # the driver's 8-GPU command, rehearsed with eight ranks on the one GPU (the numbers mean nothing; the line's shape does)
-  BSX_BENCH_BACKEND=gloo BSX_BENCH_SINGLE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_8ranks_on_one_gpu_gloo.json
+  BSX_BENCH_BACKEND=gloo BSX_BENCH_SINGLE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 20 --warmup 5 --full --no-cpu-baseline 2>/dev/null | grep '^{' > $out/bench_8ranks_on_one_gpu_gloo.json
   timeout 300 python tools/physics_error.py > $out/physics_error.log 2>&1; cp gpurun_out/physics_error.json $out/ 2>/dev/null
   timeout 300 python tools/fuzz_gpu.py --seconds ${FUZZ_SECONDS:-300} --seed 11 > $out/fuzz_gpu.log 2>&1; tail -1 $out/fuzz_gpu.log
   # the engine against the UNMODIFIED reference, live: 8 x LIVE_CASES random cases (families, kwargs, wrappers, resets, policies)
