@@ -19,17 +19,6 @@
 typedef float bsx_f4 __attribute__((ext_vector_type(4)));
 typedef float bsx_f2 __attribute__((ext_vector_type(2)));
 
-// Which per-lane OUTPUT stores take a cache policy other than plain — non-temporal in a fused rollout, write-through in an
-// eager step (bsx_st below) — as bits (-DBSX_SMALL_NT=<n> in measurement builds, tools/ab_flag_lib.py):
-//   1  reward / discount / step_type columns (a wave's store is one contiguous 256- / 64-byte range)
-//   2  observation rows of one or two floats stored by their own thread (contiguous per wave as well)
-//   4  rows staged through a wave's LDS and stored as 16-byte chunks (full lines)
-//   8  rows of 4 / 6 / 8 floats stored by their own thread as 8-byte pieces at the row stride (partial lines)
-//  16  rows of three floats (one 12-byte store per lane, contiguous per wave)
-//  32  the 16-byte chunks of the wide rows' LDS bit-plane tiles (memory_chain, umbrella_chain)
-#ifndef BSX_SMALL_NT
-#define BSX_SMALL_NT 55        // 1 + 2 + 4 + 16 + 32: everything but the partial-line rows (small_obs.h has the measurements)
-#endif
 // Cache policy of an OUTPUT store.  PLAIN; NT = non-temporal (`nt`): the lines neither stay in L2 nor allocate in the Infinity
 // Cache; WT = write-through (`sc1`): they leave L2 for the memory side at once but DO land in the Infinity Cache.
 // Which one pays depends on who reads the output next (round 6, profiles/r06/ab_store_cache_policies.log,
@@ -41,7 +30,10 @@ typedef float bsx_f2 __attribute__((ext_vector_type(2)));
 enum { BSX_ST_PLAIN = 0, BSX_ST_NT = 1, BSX_ST_WT = 2 };
 // (the write-through stores are inline asm — no builtin sets sc1 alone — and end with `s_nop 1`: the compiler's hazard
 // recognizer does not look inside an asm string, and a VALU write of the data registers right behind a store of more than
-// 8 bytes is a hazard on gfx9: without it mountain_car's 12-byte rows came out corrupted on a few lanes per wave)
+// 8 bytes is a hazard on gfx9: without it mountain_car's 12-byte rows came out corrupted on a few lanes per wave.
+// Invariant of every caller: an sc1 store only ever targets global memory — `global_store ... off` takes the generic pointer
+// as a global address — and nothing in the kernel reads its bytes back: the compiler's wait-count insertion does not count
+// a store it cannot see, so no later load of the same address would wait for it.)
 #if defined(__HIP_DEVICE_COMPILE__)
 template <int BYTES> struct bsx_wt_store;
 template <> struct bsx_wt_store<1> { template <class T> __device__ static __forceinline__ void go(const void* p, T v) { uint32_t w = 0; __builtin_memcpy(&w, &v, 1); asm volatile("global_store_byte %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory"); } };
@@ -60,17 +52,6 @@ __device__ __forceinline__ void bsx_st(P* p, V v) {
   *p = (P)v;
 #endif
 }
-// policy of an output kind (a bit of BSX_SMALL_NT) in a fused rollout (R) / in an eager step (E)
-#define BSX_POLICY_R(bit) ((BSX_SMALL_NT & (bit)) ? BSX_ST_NT : BSX_ST_PLAIN)
-#if defined(BSX_AB_EAGER_NT)           // measurement builds only: the eager step's outputs non-temporal as well
-#define BSX_POLICY_E(bit) ((BSX_SMALL_NT & (bit)) ? BSX_ST_NT : BSX_ST_PLAIN)
-#else
-#define BSX_POLICY_E(bit) ((BSX_SMALL_NT & (bit)) ? BSX_ST_WT : BSX_ST_PLAIN)
-#endif
-#ifndef BSX_TILE64_POLICY
-#define BSX_TILE64_POLICY BSX_ST_WT     // the 64-lane tiles of a small catch batch (an eager step: write-through)
-#endif
-
 // Per-call values every kernel needs, flattened out of bsx_call_t on the host.
 struct bsx_ctl {
   int64_t n_lanes;
@@ -117,7 +98,7 @@ __host__ __device__ __forceinline__ bool bsx_ctl_lean(const bsx_ctl& c) {
 // device memory (hardware f64 atomics do not reach fine-grained host mappings): include/bsuite_amd.h says so.
 // `quiet`: no Logging wrapper reads the column in this launch (bsx_track snapshots it).
 __device__ __forceinline__ void bsx_info_add(bool quiet, double* p, double v) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BSX_NO_INFO_ATOMICS)
+#if defined(__HIP_DEVICE_COMPILE__)
   if (quiet) { __builtin_amdgcn_global_atomic_fadd_f64((__attribute__((address_space(1))) double*)p, v); return; }
 #endif
   *p += v;
@@ -260,7 +241,7 @@ __device__ __forceinline__ void bsx_emit_values(const bsx_ctl& c, int64_t i, int
 
 // Writes the scalar TimeStep fields of one lane (coalesced: lane i -> element oi of each column;
 // oi == i for step(), oi == t*B + i inside a fused T-step rollout).
-// POLICY: other than plain stores (BSX_SMALL_NT bit 1) ONLY where every lane of a wave emits, lane by lane (the small-observation
+// POLICY: other than plain stores (the scalar columns' policy, small_obs.h) ONLY where every lane of a wave emits, lane by lane (the small-observation
 // kernels): a wave's store is then one contiguous range.  A lone emitting thread (the writer threads of deep_sea's
 // single-launch step: one lane per 225 threads) must not — 4-byte non-temporal stores scattered over the grid took that
 // kernel from 81 to 125 us at 2^17 lanes.
@@ -294,26 +275,13 @@ __device__ __forceinline__ void bsx_count_types(const bsx_ctl& c, int type, unsi
   }
 }
 
-// Measurement builds only (-DBSX_TRACE_LIFE, tools/sweep_phase0_trace.py --life): thread 0 of every workgroup of the
-// sweep's phase 0 stamps the wall clock at up to 8 points of its life into bsx_life_trace_ptr[8 * blockIdx.x + k].
-#ifdef BSX_TRACE_LIFE
-static __device__ uint64_t* bsx_life_trace_ptr;
-#define BSX_LIFE(k) do { if (threadIdx.x == 0 && bsx_life_trace_ptr != nullptr) bsx_life_trace_ptr[8 * (size_t)blockIdx.x + (k)] = wall_clock64(); } while (0)
-#define BSX_LIFE_AFTER_V(k, v) do { asm volatile("" :: "v"(v)); BSX_LIFE(k); } while (0)
-#define BSX_LIFE_AFTER_S(k, v) do { asm volatile("" :: "s"(v)); BSX_LIFE(k); } while (0)
-#else
-#define BSX_LIFE(k) do {} while (0)
-#define BSX_LIFE_AFTER_V(k, v) do {} while (0)
-#define BSX_LIFE_AFTER_S(k, v) do {} while (0)
-#endif
-
 // The LAST barrier of a workgroup, in front of bsx_flush_counts: it has to order the waves' LDS counter updates and
 // nothing else.  __syncthreads() is a fence + barrier, and on gfx9 its release half waits for vmcnt(0) — every wave
 // sat through the acknowledgements of its final stores (1-3 us behind a saturated memory system) before it could
 // arrive, and the workgroup's slot stayed taken for that long; the waves may simply END with their stores in flight
-// (the kernel's completion covers them).  BSX_FINAL_BARRIER_FENCED restores the old form for A/B builds.
+// (the kernel's completion covers them).
 __device__ __forceinline__ void bsx_final_barrier() {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(BSX_FINAL_BARRIER_FENCED)
+#if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #else
   __syncthreads();
@@ -442,21 +410,16 @@ __device__ __forceinline__ void bsx_advance_body(const typename Fam::args& a, ui
     const uint64_t lane = a.ctl.lane_offset + (uint64_t)i;
     const uint64_t step = bsx_step_of(a.ctl);
     int32_t nst; double reward;
-    BSX_LIFE_AFTER_S(2, (uint32_t)step);                    // the argument slot and the call counter have arrived
     const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, i, step);
     const int32_t st = a.ctl.state_in != nullptr ? a.ctl.state_in[i] : a.state[i];
-    BSX_LIFE_AFTER_V(3, st + act);                              // ... the lane's state and action
     type = bsx_fam_advance<Fam, LEAN, MT == 0>(a, s_fam, i, lane, step, st, act, nst, reward);
-    BSX_LIFE_AFTER_V(4, nst);                                   // ... computed
     a.state[i] = nst;
     if (s_state != nullptr) s_state[threadIdx.x] = nst;     // fused small-batch step: the tile streamer reads it from LDS
     if (LEAN) bsx_emit_at<0, 0, false>(a.ctl, a.out, i, i, lane, step, type, reward);
     else bsx_emit_at<-1, -1, true, MT>(a.ctl, a.out, i, i, lane, step, type, reward);
   }
-  BSX_LIFE(5);                                                  // stores issued
   bsx_count_types(a.ctl, type, s_cnt);
   bsx_final_barrier();
-  BSX_LIFE(6);
   bsx_flush_counts(a.ctl, s_cnt, block_id);
 }
 
@@ -527,10 +490,6 @@ __device__ __forceinline__ void bsx_hot_stream_body(float* __restrict__ obs,
                                                     int64_t n_lanes, uint32_t cells,
                                                     uint32_t cells_magic, bsx_div64 dv,
                                                     const HotFn& fn, uint32_t block_id, int wave_contig = 1) {
-#ifdef BSX_TUNING
-  const int pace = wave_contig >> 8;                                     // BSX_STREAM_PACE (bsx_launch_hot_stream)
-  wave_contig &= 1;
-#endif
   const uint64_t total = (uint64_t)n_lanes * cells;                      // floats in the array
   const uint64_t F0 = (uint64_t)block_id * (uint64_t)(K * 4 * BS);
   const uint64_t lane_b = __umul64hi(F0, dv.m) >> dv.s;                  // uniform
@@ -561,17 +520,9 @@ __device__ __forceinline__ void bsx_hot_stream_body(float* __restrict__ obs,
     dl[u] = __umulhi(f, cells_magic);
     r0[u] = (int)(f - dl[u] * cells);
     live[u] = F0 + ((uint64_t)c << 2) + 3 < total;
-#if defined(BSX_ABLATE_STREAM_LOADS)      // measurement builds only (tools/ab/): the store stream without its state loads
-    s0[u] = live[u] ? (int32_t)(dl[u] * 7u + (uint32_t)lane_b) & 0x0F0F : 0;
-    s1[u] = s0[u] + 1;
-#else
     s0[u] = live[u] ? st[dl[u]] : 0;
     s1[u] = (live[u] && !aligned && (uint64_t)dl[u] + 1 < lanes_left) ? st[dl[u] + 1] : 0;
-#endif
   }
-#ifdef BSX_TUNING
-  for (int q = 0; q < pace; ++q) __builtin_amdgcn_s_sleep(16);           // 16 x 64 clocks per round
-#endif
 #pragma unroll
   for (int u = 0; u < K; ++u) {
     if (!live[u]) continue;
@@ -726,7 +677,7 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_fused_tile64_kernel(const typen
   }
   __syncthreads();
   const int64_t left = a.ctl.n_lanes - lane0;
-  bsx_tile_stream<HotFn, BSX_TILE64_POLICY>(obs + lane0 * (int64_t)cells, s_state, left < BSX_WAVE ? (int)left : BSX_WAVE, cells, cells_magic, fn);
+  bsx_tile_stream<HotFn, BSX_ST_WT>(obs + lane0 * (int64_t)cells, s_state, left < BSX_WAVE ? (int)left : BSX_WAVE, cells, cells_magic, fn);
 }
 
 // The same for a rollout of T steps: ONE launch.  Lanes never interact, so a workgroup can take its 256 lanes
@@ -791,11 +742,7 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_pipelined_kernel(const typename
   __shared__ unsigned int s_cnt[2];
   const bsx_pipe_role r = bsx_pipe_role_of(blockIdx.x, gridDim.x, adv_blocks, place);   // uniform per workgroup
   if (r.adv) bsx_advance_body<Fam, LEAN>(a, r.index, s_fam, s_cnt);
-#if defined(BSX_AB_PIPELINED_NT)     // measurement builds only: non-temporal stores in the pipelined rollout's stream half
-  else bsx_hot_stream_body<HotFn, K, BSX_BLOCK, true>(obs, hot_state, a.ctl.n_lanes, cells, cells_magic, dv, fn, r.index);
-#else
   else bsx_hot_stream_body<HotFn, K, BSX_BLOCK>(obs, hot_state, a.ctl.n_lanes, cells, cells_magic, dv, fn, r.index);
-#endif
 }
 
 template <class HotFn, int K>

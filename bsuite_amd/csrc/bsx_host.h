@@ -99,8 +99,7 @@ template <class Fam>
 static inline int bsx_launch_advance(const typename Fam::args& a, hipStream_t st) {
   const int64_t blocks = (a.ctl.n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
-  static const int lean_env = bsx_env_int("BSX_ADVANCE_LEAN", 1);
-  const bool lean = lean_env != 0 && bsx_ctl_lean(a.ctl);
+  const bool lean = bsx_ctl_lean(a.ctl);
   // From two dispatch rounds of one-lane workgroups up (2^20 lanes): two lanes per thread, both lanes' loads issued up
   // front — ONE round.  Same call (profiles/r04/ab_advance_two_lanes.log): catch/0 42.5 -> 41.6 us per step, deep_sea -0.5 us;
   // equal at 2^19 lanes, 79.8 -> 78.8 at 2^21.  (0 = never)
@@ -128,8 +127,9 @@ static inline bsx_div64 bsx_make_div64(uint32_t d) {
 }
 
 // Launches the split-phase observation writer: K stores per thread, 256 threads per workgroup — each family's measured
-// optimum (profiles/r01/sweep_stream_*.log), the only shape the product library contains.  The tuning build compiles the
-// whole K x block-size matrix and picks by BSX_STREAM_K / BSX_STREAM_BS / BSX_STREAM_WAVE_CONTIG.
+// optimum (profiles/r01/sweep_stream_*.log) — in the wave-contiguous order.  (That order is a run-time argument that is
+// always 1: folded into the kernel at compile time, the compiler schedules the headline's stream differently and it ran
+// 0.2 % slower, deep_sea/10 at 2^20 lanes 0.5913 -> 0.5926 ms per step, A/B/B/A in one call.)
 template <class HotFn, int K>
 static inline int bsx_launch_hot_stream(float* obs, const int32_t* state, int64_t n_lanes, uint32_t cells,
                                         uint32_t cells_magic, HotFn fn, hipStream_t st) {
@@ -143,38 +143,11 @@ static inline int bsx_launch_hot_stream(float* obs, const int32_t* state, int64_
     return 0;
   }
   const bsx_div64 dv = bsx_make_div64(cells);
-#ifndef BSX_TUNING
   const uint64_t per_block = (uint64_t)K * 4 * BSX_BLOCK;
   const uint64_t blocks = (total + per_block - 1) / per_block;
   if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
   bsx_hot_stream_kernel<HotFn, K, BSX_BLOCK><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(obs, state, n_lanes, cells, cells_magic, dv, fn, 1);
   return 0;
-#else
-  static const int k_env = bsx_env_int("BSX_STREAM_K", 0);
-  const int k = k_env > 0 ? k_env : K;
-  static const int bs_env = bsx_env_int("BSX_STREAM_BS", 256);
-  static const int ks[] = {1, 2, 3, 4, 5, 6, 8, 12, 16};
-  int kk = 1;
-  for (int i = 0; i < 9; ++i) if (ks[i] <= k) kk = ks[i];
-  const int bs = bs_env >= 1024 ? 1024 : bs_env >= 512 ? 512 : bs_env >= 256 ? 256 : bs_env >= 128 ? 128 : 64;
-  const uint64_t per_block = (uint64_t)kk * 4 * bs;
-  const uint64_t blocks = (total + per_block - 1) / per_block;
-  if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
-  const dim3 g((unsigned)blocks);
-  // BSX_STREAM_LDS: dynamic LDS nobody uses = fewer workgroups per CU; BSX_STREAM_PACE: s_sleep rounds before the stores
-  static const int wave_contig = bsx_env_int("BSX_STREAM_WAVE_CONTIG", 1) | (bsx_env_int("BSX_STREAM_PACE", 0) << 8);
-  static const int lds = bsx_env_int("BSX_STREAM_LDS", 0);
-#define BSX_HS(KK, BS) case KK: bsx_hot_stream_kernel<HotFn, KK, BS><<<g, dim3(BS), (size_t)lds, st>>>(obs, state, n_lanes, cells, cells_magic, dv, fn, wave_contig); break
-#define BSX_HS_ALL(BS) switch (kk) { BSX_HS(1, BS); BSX_HS(2, BS); BSX_HS(3, BS); BSX_HS(4, BS); BSX_HS(5, BS); BSX_HS(6, BS); BSX_HS(8, BS); BSX_HS(12, BS); BSX_HS(16, BS); default: return BSX_EINVAL; }
-  if (bs == 256) { BSX_HS_ALL(256) }
-  else if (bs == 128) { BSX_HS_ALL(128) }
-  else if (bs == 512) { BSX_HS_ALL(512) }
-  else if (bs == 1024) { BSX_HS_ALL(1024) }
-  else { BSX_HS_ALL(64) }
-#undef BSX_HS_ALL
-#undef BSX_HS
-  return 0;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -283,7 +256,7 @@ static inline int bsx_launch_status() { return (int)hipGetLastError(); }
 //                                   stream(T-1) — T+1 launches.  The advances alternate between `state`
 //                                   and `state_alt` so that the column stream(t) reads is not the one
 //                                   advance(t+1) writes; the parity is chosen so that the last advance
-//                                   writes `state`.  BSX_ROLLOUT_PIPELINED=0: A/B.
+//                                   writes `state`.
 template <class Fam, class HotFn, int K>
 static int bsx_pair_call(const typename Fam::args& a0, const bsx_call_t* call, const int32_t* action, int32_t* state,
                          bsx_timestep_t out, uint32_t cells, const HotFn& fn) {
@@ -301,15 +274,14 @@ static int bsx_pair_call(const typename Fam::args& a0, const bsx_call_t* call, c
     return s;
   };
   const uint32_t magic = bsx_div_magic(cells);
-  static const int pipe_env = bsx_env_int("BSX_ROLLOUT_PIPELINED", 1);
   static const int place = bsx_env_int("BSX_PIPELINED_PLACE", 0);     // bsx_pipe_role_of: first (measured best)
   // the fused launch uses the 16-byte store stream: every [t] slice must start on a 16-byte boundary
-  const bool pipelined = pipe_env != 0 && T > 1 && call->state_alt != nullptr && call->obs_paint == nullptr &&
+  const bool pipelined = T > 1 && call->state_alt != nullptr && call->obs_paint == nullptr &&
                          cells >= 4u && (((uint64_t)B * cells) & 3ull) == 0;
   int rc = 0;
   // Boards of at most BSX_FUSED_TILE_MAX_CELLS floats (catch's 50; a workgroup's [256 x cells] tile is then <= 128 KiB):
   // ONE fused launch per step (bsx_fused_tile_kernel) and ONE per rollout (bsx_fused_rollout_kernel) while the
-  // observation array of a step is at most BSX_FUSED_TILE_MAX_MIB / BSX_FUSED_ROLLOUT_MAX_MIB = 128 MiB: catch up to
+  // observation array of a step is at most fused_step_mib / BSX_FUSED_ROLLOUT_MAX_MIB = 128 MiB: catch up to
   // 2^19 lanes (105 MB: 20 vs 23 us eager, 20 vs 22 us per rollout step; 2^17: 9.4 vs 11 and 7.1 vs 9.0).  At 2^20
   // lanes (210 MB) the winner depends on the box — fused 41.9 vs 43.5 on one, 44.4-45.2 vs 43.2-43.6 on another; a
   // rollout 36.9 vs 39.6 and 43.4-45.5 vs 39.7-40.9 (its T slices lie 210 MB apart: page-mapping luck) — so the
@@ -320,11 +292,12 @@ static int bsx_pair_call(const typename Fam::args& a0, const bsx_call_t* call, c
   // per workgroup with both tiles' inputs loaded up front, i.e. one dispatch round at 2^20 lanes: 42.7-45.2 vs
   // 41.1-41.7 us for the pair, profiles/r03/ab_fused_tiles_per_wg.log.)
   static const int fused_cells = bsx_env_int("BSX_FUSED_TILE_MAX_CELLS", 128);
-  static const int fused_step_mib = bsx_env_int("BSX_FUSED_TILE_MAX_MIB", 128);
+  constexpr int fused_step_mib = 128;
   static const int fused_roll_mib = bsx_env_int("BSX_FUSED_ROLLOUT_MAX_MIB", 128);
   // (64-lane tiles up to 2^18 lanes: catch 2^15 7.3 -> 5.6 us, 2^16 8.1 -> 6.0, 2^17 9.1 -> 8.0 (r04, ordinary stores:
-  // profiles/r04/ab_catch_fused_tile64.log; 2^18 was 12.3 -> 12.7 then); with their chunks non-temporal (round 6) 2^17 8.0 ->
-  // 6.8 and 2^18 12.2 -> 11.55, 2^19 19.3 -> 19.8: profiles/r06/ab_catch_tile64_nt_larger_batches.log)
+  // profiles/r04/ab_catch_fused_tile64.log; 2^18 was 12.3 -> 12.7 then); re-measured in round 6 with non-temporal chunks, 2^17
+  // 8.0 -> 6.8, 2^18 12.2 -> 11.55, 2^19 19.3 -> 19.8 (profiles/r06/ab_catch_tile64_nt_larger_batches.log): the limit stayed.
+  // The chunks the product stores are write-through (bsx_fused_tile64_kernel, bsx_tile_stream has the measurements).)
   static const int64_t tile64_max_lanes = bsx_env_int("BSX_FUSED_TILE64_MAX_LANES", 1 << 18);
   const int64_t step_bytes = B * (int64_t)cells * 4;
   const bool fusable = call->obs_paint == nullptr && cells >= 4u && (int)cells <= fused_cells &&

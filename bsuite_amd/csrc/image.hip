@@ -254,10 +254,8 @@ extern "C" int bsx_image_observation(const bsx_image_t* cfg, int64_t n_lanes, co
   // Run length per workgroup: every workgroup re-stages its lane's observation and rebuilds the axis
   // tables before its first store, so large observations want longer runs (measured on 84x84x4,
   // profiles/r01/ab_image_k.log: 10x5 input best at 4 KiB x 4, 30x30 at x16; images whose
-  // channel count is not a multiple of 4 evaluate up to four pixels per store and prefer x8).  BSX_IMAGE_K overrides.
-  static const int k_knob = bsx_env_int("BSX_IMAGE_K", 0);
-  const int k = (k_knob == 2 || k_knob == 4 || k_knob == 8 || k_knob == 16) ? k_knob
-                : (in_numel > 256 && (cfg->tail & 3) == 0 ? 16 : (in_numel > 64 ? 8 : 4));
+  // channel count is not a multiple of 4 evaluate up to four pixels per store and prefer x8).
+  const int k = in_numel > 256 && (cfg->tail & 3) == 0 ? 16 : (in_numel > 64 ? 8 : 4);
   const int64_t run = (int64_t)k * BSX_BLOCK * 4;
   a.blocks_per_lane = (uint32_t)((numel + run - 1) / run);
   const int64_t blocks = n_lanes * (int64_t)a.blocks_per_lane;
@@ -272,7 +270,6 @@ extern "C" int bsx_image_observation(const bsx_image_t* cfg, int64_t n_lanes, co
     for (int j = 0; j <= cfg->radius_x; ++j) gw.w[1][j] = cfg->gauss_x[j];
   }
   switch (k) {
-    case 2: bsx_image_kernel<2><<<grid, block, lds, st>>>(a, gw); break;
     case 8: bsx_image_kernel<8><<<grid, block, lds, st>>>(a, gw); break;
     case 16: bsx_image_kernel<16><<<grid, block, lds, st>>>(a, gw); break;
     default: bsx_image_kernel<4><<<grid, block, lds, st>>>(a, gw); break;

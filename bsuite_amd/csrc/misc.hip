@@ -219,8 +219,7 @@ static int group_commit(bsx_group* g) {
   if (rc == 0) rc = upload(start2.data(), start2.size() * 4, (void**)&g->d_start2);
   // (segment, local block) of every workgroup: one load per workgroup instead of a binary search;
   // launches beyond 2^24 workgroups (128 MiB of map) keep the search.
-  static const int use_map = bsx_env_int("BSX_GROUP_MAP", 1);
-  for (int pass = 0; pass < 2 && rc == 0 && use_map; ++pass) {
+  for (int pass = 0; pass < 2 && rc == 0; ++pass) {
     const int64_t total = pass == 0 ? t1 : t2;
     const std::vector<int32_t>& blocks = pass == 0 ? g->blocks : g->blocks2;
     if (total == 0 || total > (1 << 24)) continue;

@@ -164,10 +164,6 @@ __device__ __forceinline__ void mnist_observe_body_nt(const mnist_observe_args& 
 
 template <int K>
 __device__ __forceinline__ void mnist_observe_body(const mnist_observe_args& a, uint32_t block_id, float* s_lut) {
-#if defined(BSX_AB_MNIST_NT)        // measurement builds only
-  mnist_observe_body_nt<K, true>(a, block_id, s_lut);
-  return;
-#endif
   if (a.nt) mnist_observe_body_nt<K, true>(a, block_id, s_lut);                                // uniform
   else mnist_observe_body_nt<K, false>(a, block_id, s_lut);
 }

@@ -47,13 +47,10 @@ int bsx_sweep_launch_pipelined(bsx_group* streams_of, bsx_group* advances_of, hi
 #ifndef PAIR_CATCH_K
 #define PAIR_CATCH_K 2
 #endif
-// non-temporal stores for the one-hot bodies of the MIXED stream (bsx_hot_stream_body<..., NT>): what the other workgroups of the
+// non-temporal stores for the one-hot bodies of the MIXED stream (bsx_hot_stream_body<..., NT = true> below): what the other workgroups of the
 // launch and the next launch want to find in cache — state columns, action ring, tables, the small families' columns — is no
 // longer evicted by 420 MB of deep_sea / catch observations per sweep step.  Not for the mnist body (its image gathers like
 // ordinary neighbours: 165-171 us with nt on mnist alone, 157-169 with both; profiles/r06/ab_nontemporal_stores*.log)
-#ifndef PAIR_HOT_NT
-#define PAIR_HOT_NT true
-#endif
 // (The segments' pointers arrive through the argument table, so the compiler emits FLAT loads and stores here.  Typed as
 // global memory — global_store_dwordx4, no lgkmcnt traffic — the closed-loop sweep step is SLOWER: 159.4-161.9 us against
 // 151.2-159.5, same call, four repetitions; profiles/r06/ab_sweep_global_pointers.log.  Left as the compiler has it.)
@@ -64,12 +61,12 @@ __device__ __forceinline__ void pair_mixed_stream_body(const uint8_t* __restrict
   switch (w.tag >= 0 ? w.tag : (family[w.seg] & 0xFF)) {   // uniform per workgroup
     case BSX_FAM_DEEP_SEA: {
       const bsx_stream_seg<deep_sea_hot>& g = *reinterpret_cast<const bsx_stream_seg<deep_sea_hot>*>(slot);
-      bsx_hot_stream_body<deep_sea_hot, PAIR_DEEP_SEA_K, BSX_BLOCK, PAIR_HOT_NT>(g.obs, g.state, g.n_lanes, g.cells, g.cells_magic, g.dv, g.fn, w.block);
+      bsx_hot_stream_body<deep_sea_hot, PAIR_DEEP_SEA_K, BSX_BLOCK, true>(g.obs, g.state, g.n_lanes, g.cells, g.cells_magic, g.dv, g.fn, w.block);
       break;
     }
     case BSX_FAM_CATCH: {
       const bsx_stream_seg<catch_hot>& g = *reinterpret_cast<const bsx_stream_seg<catch_hot>*>(slot);
-      bsx_hot_stream_body<catch_hot, PAIR_CATCH_K, BSX_BLOCK, PAIR_HOT_NT>(g.obs, g.state, g.n_lanes, g.cells, g.cells_magic, g.dv, g.fn, w.block);
+      bsx_hot_stream_body<catch_hot, PAIR_CATCH_K, BSX_BLOCK, true>(g.obs, g.state, g.n_lanes, g.cells, g.cells_magic, g.dv, g.fn, w.block);
       break;
     }
     case BSX_FAM_MNIST:

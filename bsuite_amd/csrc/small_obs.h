@@ -82,7 +82,7 @@ struct bsx_reset_pool {
   unsigned int n[2];                 // how many; [step parity]
 };
 
-// The cache policy of the OUTPUT stores (bsx_st<POLICY>, BSX_SMALL_NT: bsx_device.h; round 6).  What a step or a rollout writes —
+// The cache policy of the OUTPUT stores (bsx_st<POLICY>: bsx_device.h; round 6).  What a step or a rollout writes —
 // TimeStep columns and observation rows — is never read again by the engine, while what it READS (actions a run ahead, state
 // and info columns, tables) is what the stores evict: the fused rollouts were bound by exactly those reads (r04: 6.5 us with,
 // 4.8 without the action loads).  A FUSED ROLLOUT's outputs are NON-TEMPORAL wherever a wave's store instruction covers one
@@ -94,40 +94,52 @@ struct bsx_reset_pool {
 // cartpole 17.7 -> 15.8 us, discounting_chain 7.05 -> 6.05, memory_len 10.0 -> 9.25, bandit 8.46 -> 7.96, the closed loop equal or
 // faster everywhere (ab_eager_output_policy.log).  NEITHER for rows written as 8-byte pieces at the row stride (cartpole
 // row-per-lane: 18 -> 25 us non-temporal — partial lines want the L2 to merge them).  deep_sea / catch / mnist / the sweep are
-// not touched by this (ab_small_nt_other_paths.log).  Per family: does the fused rollout store reward / discount / step_type
-// non-temporal?
+// not touched by this (ab_small_nt_other_paths.log).  The policy of each kind of output, in a fused rollout and in an eager step:
+struct bsx_out_policy { int rollout, eager; };
+constexpr bsx_out_policy BSX_OUT_SCALARS = {BSX_ST_NT, BSX_ST_WT};        // reward / discount / step_type columns (a wave's store is
+                                                                          // one contiguous 256- / 64-byte range)
+constexpr bsx_out_policy BSX_OUT_ROW12 = {BSX_ST_NT, BSX_ST_WT};          // rows of one or two floats stored by their own thread
+constexpr bsx_out_policy BSX_OUT_STAGED = {BSX_ST_NT, BSX_ST_WT};         // rows staged through a wave's LDS, stored as 16-byte chunks
+constexpr bsx_out_policy BSX_OUT_PARTIAL = {BSX_ST_PLAIN, BSX_ST_PLAIN};  // rows of 4 / 6 / 8 floats stored by their own thread as
+                                                                          // 8-byte pieces at the row stride (partial lines)
+constexpr bsx_out_policy BSX_OUT_ROW3 = {BSX_ST_NT, BSX_ST_WT};           // rows of three floats (one 12-byte store per lane)
+constexpr bsx_out_policy BSX_OUT_TILE = {BSX_ST_NT, BSX_ST_WT};           // the 16-byte chunks of the wide rows' bit-plane tiles
+constexpr int bsx_policy(bsx_out_policy p, bool rollout) { return rollout ? p.rollout : p.eager; }
+// Per family: does the fused rollout store reward / discount / step_type non-temporal?
 template <class Env> struct small_rollout_nt_scalars { static constexpr bool value = true; };
 
 // A lane's own thread stores its short row (<= 8 floats).  A wave's 64 rows are one contiguous range, written by
 // back-to-back instructions that the L2 merges line by line.
 template <bool ROLLOUT_ST>
 __device__ __forceinline__ void small_obs_store_row(float* __restrict__ dst, const float* o, int numel) {
-  constexpr int P2 = ROLLOUT_ST ? BSX_POLICY_R(2) : BSX_POLICY_E(2), P8 = ROLLOUT_ST ? BSX_POLICY_R(8) : BSX_POLICY_E(8);
+  constexpr int P12 = bsx_policy(BSX_OUT_ROW12, ROLLOUT_ST), P3 = bsx_policy(BSX_OUT_ROW3, ROLLOUT_ST);
+  constexpr int PP = bsx_policy(BSX_OUT_PARTIAL, ROLLOUT_ST);
   if ((numel & 1) == 0) {
     bsx_f2* __restrict__ d2 = reinterpret_cast<bsx_f2*>(dst);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       if (2 * k < numel) {
         bsx_f2 v; v.x = o[2 * k]; v.y = o[2 * k + 1];
-        if (numel == 2) bsx_st<P2>(&d2[k], v);
-        else bsx_st<P8>(&d2[k], v);
+        if (numel == 2) bsx_st<P12>(&d2[k], v);
+        else bsx_st<PP>(&d2[k], v);
       }
   } else if (numel == 3) {
-    // one 12-byte store per lane (global_store_dwordx3): a wave's 64 rows are 768 contiguous bytes
-    if (ROLLOUT_ST && (BSX_SMALL_NT & 16)) {
+    // one 12-byte store per lane (global_store_dwordx3): a wave's 64 rows are 768 contiguous bytes.  (The non-temporal builtin
+    // takes a 3-float vector, not a struct; bsx_st's write-through store is sized by sizeof, which is 16 for that vector.)
+    if constexpr (P3 == BSX_ST_NT) {
       typedef float row3v __attribute__((ext_vector_type(3), aligned(4)));
       row3v v; v.x = o[0]; v.y = o[1]; v.z = o[2];
       __builtin_nontemporal_store(v, reinterpret_cast<row3v*>(dst));
     } else {
       struct __attribute__((packed, aligned(4))) row3 { float a, b, c; };
       row3 v; v.a = o[0]; v.b = o[1]; v.c = o[2];
-      bsx_st<(ROLLOUT_ST ? BSX_ST_PLAIN : BSX_POLICY_E(16))>(reinterpret_cast<row3*>(dst), v);
+      bsx_st<P3>(reinterpret_cast<row3*>(dst), v);
     }
   } else {
 #pragma unroll
     for (int k = 0; k < 7; ++k)                                   // numel == 1, 5, 7: 4-byte stores
       if (k < numel) {
-        if (numel == 1) bsx_st<P2>(&dst[k], o[k]);
+        if (numel == 1) bsx_st<P12>(&dst[k], o[k]);
         else dst[k] = o[k];
       }
   }
@@ -157,9 +169,10 @@ __device__ __forceinline__ const BSX_GLOBAL T* bsx_at_off(const T* base, uint32_
 // a third of their bytes, three write requests per segment where one would do, and the fused rollouts of the physics
 // families turned out to be bound by exactly that (profiles/r03/exp_store_ablation.log: without the row stores
 // cartpole's step takes 8.1 us instead of 13.3).  No workgroup barrier: LDS serves a wave's accesses in order.
-// dst = row of the wave's first lane (16-byte aligned: the caller checks), s_wave = 64 * 8 floats, wl = lane in the wave.
-template <bool ROLLOUT_ST>
-__device__ __forceinline__ void small_obs_store_rows_wave(float* __restrict__ dst, const float* o, int numel, float* s_wave, int wl) {
+// chunk(c) = the address of the wave's 16-byte chunk c (its first row 16-byte aligned: the caller checks), s_wave = 64 * 8
+// floats, wl = lane in the wave.
+template <bool ROLLOUT_ST, class Chunk>
+__device__ __forceinline__ void small_obs_store_rows_wave(Chunk chunk, const float* o, int numel, float* s_wave, int wl) {
   float* mine = s_wave + wl * numel;
   if ((numel & 1) == 0) {
 #pragma unroll
@@ -175,28 +188,8 @@ __device__ __forceinline__ void small_obs_store_rows_wave(float* __restrict__ ds
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const int chunks = 16 * numel;                                 // 64 rows x numel floats / 4
   for (int c = wl; c < chunks; c += 64)
-    bsx_st<(ROLLOUT_ST ? BSX_POLICY_R(4) : BSX_POLICY_E(4))>(&reinterpret_cast<bsx_f4*>(dst)[c], reinterpret_cast<const bsx_f4*>(s_wave)[c]);
+    bsx_st<bsx_policy(BSX_OUT_STAGED, ROLLOUT_ST)>(chunk(c), reinterpret_cast<const bsx_f4*>(s_wave)[c]);
   __builtin_amdgcn_wave_barrier();                               // (the next step's rows are written after these reads)
-}
-// ... the same with the destination as {uniform slab pointer, byte offset of the wave's first row}
-__device__ __forceinline__ void small_obs_store_rows_wave_off(float* slab, uint32_t wave_off, const float* o, int numel, float* s_wave, int wl) {
-  float* mine = s_wave + wl * numel;
-  if ((numel & 1) == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (2 * k < numel) *reinterpret_cast<float2*>(mine + 2 * k) = make_float2(o[2 * k], o[2 * k + 1]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 7; ++k)
-      if (k < numel) mine[k] = o[k];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int chunks = 16 * numel;
-  for (int c = wl; c < chunks; c += 64)
-    bsx_st<BSX_POLICY_R(4)>(bsx_at_off(reinterpret_cast<bsx_f4*>(slab), wave_off + 16u * (uint32_t)c), reinterpret_cast<const bsx_f4*>(s_wave)[c]);
-  __builtin_amdgcn_wave_barrier();
 }
 
 // The same value, opaque to the optimiser: what is computed from it stays where it is written (no hoisting out of loops).
@@ -233,10 +226,7 @@ __device__ __forceinline__ void small_obs_regs_rollout(const typename Env::args&
   constexpr bool POOL = BIG && Env::POOLED_RESETS && MT == 0;
   constexpr bool ROWS = BIG && Env::ROWS_VIA_LDS;
   constexpr bool OFF32 = V >= 0;
-#ifndef BSX_RUN
-#define BSX_RUN 8
-#endif
-  constexpr int RUN = OFF32 ? BSX_RUN : 8;                // (16: no drain inside a T=16 launch at all, and 3-7 % slower — profiles/r03/ab_rollout_run16.log)
+  constexpr int RUN = 8;                // (16: no drain inside a T=16 launch at all, and 3-7 % slower — profiles/r03/ab_rollout_run16.log)
   if (threadIdx.x < 2) {
     s_cnt[threadIdx.x] = 0;
     if constexpr (POOL) s_pool->n[threadIdx.x] = 0;
@@ -301,7 +291,7 @@ __device__ __forceinline__ void small_obs_regs_rollout(const typename Env::args&
     // of the wave holds an action outside 0..15 re-reads its actions from memory step by step instead (wave-uniform
     // branch; the wait it needs drains the wave's stores — slow, exact, and never taken by in-spec actions).
     int acts[OFF32 ? 1 : RUN];
-    typename std::conditional<(RUN > 8), uint64_t, uint32_t>::type packed = 0;
+    uint32_t packed = 0;
     bool wide = false;
     const int32_t* const ap_run = ap;
     if constexpr (OFF32) {
@@ -310,15 +300,8 @@ __device__ __forceinline__ void small_obs_regs_rollout(const typename Env::args&
         const uint32_t off = bsx_fresh(iu0) * 4u;
 #pragma unroll
         for (int j = 0; j < RUN; ++j) {
-#if defined(BSX_ABLATE_STORES) && (BSX_ABLATE_STORES & 4)
-          const uint32_t aj = (iu0 + (uint32_t)(t0 + j)) % 3u;           // measurement builds: the loop without its action loads
-#elif defined(BSX_ABLATE_STORES) && (BSX_ABLATE_STORES & 8)
-          uint32_t aj = (uint32_t)*bsx_at_off(ap, off);                  // ... with the loads, but the same periodic actions
-          if (aj != 0x7FFFFFF0u) aj = (iu0 + (uint32_t)(t0 + j)) % 3u;
-#else
           const uint32_t aj = (uint32_t)*bsx_at_off(ap, off);
-#endif
-          packed |= (decltype(packed))(aj & 15u) << (4 * j);
+          packed |= (aj & 15u) << (4 * j);
           wide |= aj > 15u;
           if (j + 1 < run) ap += B;                                      // uniform
         }
@@ -343,7 +326,7 @@ __device__ __forceinline__ void small_obs_regs_rollout(const typename Env::args&
       int type = -1;
       int act;
       if constexpr (OFF32) {
-        act = (int)((uint32_t)(packed >> (4 * j)) & 15u);
+        act = (int)((packed >> (4 * j)) & 15u);
         if (ap_wide != nullptr) {
           act = mine ? *bsx_at_off(ap_wide + (int64_t)j * B, bsx_fresh(iu0) * 4u) : 0;
           __builtin_amdgcn_s_waitcnt(0x0070);                            // landed: nothing pends beyond this block
@@ -383,34 +366,27 @@ __device__ __forceinline__ void small_obs_regs_rollout(const typename Env::args&
         double reward = 0.0;
         float o[8];
         type = Env::template core<LOG, MT, IREGS, TAB, POOL, V, true>(a, rg, act, i, lane, step0 + (uint64_t)t, o, reward, s_tab, s_pool);
-        // Measurement builds only (-DBSX_ABLATE_STORES, tools/ablate_stores.sh; never the product library): the loop
-        // without its observation rows (bit 0), without reward / discount / step_type (bit 1), without action loads (bit 2) — the conditions are
-        // never true, the stores stay reachable so that the arithmetic feeding them is not compiled away.
-#if defined(BSX_ABLATE_STORES)
-        const bool scalars = !(BSX_ABLATE_STORES & 2) || (reward == 123.0 && type == 7);
-        const bool rows = !(BSX_ABLATE_STORES & 1) || (o[0] == 123.0f && o[1] == 5.0f && o[2] == 7.0f);
-#else
-        constexpr bool scalars = true, rows = true;
-#endif
-        if (scalars) {
-          if constexpr (OFF32) {
-            float r, d;
-            bsx_emit_values<LOG, NOISE, F64, MT>(a.ctl, i, oi, lane, step0 + (uint64_t)t, type, reward, r, d);
-            constexpr int NTS = small_rollout_nt_scalars<Env>::value ? BSX_POLICY_R(1) : BSX_ST_PLAIN;
-            bsx_st<NTS>(bsx_at_off(rp, iu * 4u), r);
-            bsx_st<NTS>(bsx_at_off(dp, iu * 4u), d);
-            bsx_st<NTS>(bsx_at_off(sp, iu), (int8_t)type);
+        if constexpr (OFF32) {
+          float r, d;
+          bsx_emit_values<LOG, NOISE, F64, MT>(a.ctl, i, oi, lane, step0 + (uint64_t)t, type, reward, r, d);
+          constexpr int NTS = small_rollout_nt_scalars<Env>::value ? BSX_OUT_SCALARS.rollout : BSX_ST_PLAIN;
+          bsx_st<NTS>(bsx_at_off(rp, iu * 4u), r);
+          bsx_st<NTS>(bsx_at_off(dp, iu * 4u), d);
+          bsx_st<NTS>(bsx_at_off(sp, iu), (int8_t)type);
+          if (rows_via_lds) {
+            const uint32_t wave_off = (iu - (uint32_t)wl) * (uint32_t)(numel * 4);   // byte offset of the wave's first row
+            small_obs_store_rows_wave<true>([=](int c) { return bsx_at_off(reinterpret_cast<bsx_f4*>(op), wave_off + 16u * (uint32_t)c); },
+                                            o, numel, s_rows + (threadIdx.x - wl) * 8, wl);
           } else {
-            bsx_emit_at<LOG, NOISE, F64, MT, BSX_POLICY_R(1)>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
+            small_obs_store_row<true>(bsx_at_off(op, iu * (uint32_t)(numel * 4)), o, numel);
           }
-        }
-        if (rows) {
-          if constexpr (OFF32) {
-            if (rows_via_lds) small_obs_store_rows_wave_off(op, (iu - (uint32_t)wl) * (uint32_t)(numel * 4), o, numel, s_rows + (threadIdx.x - wl) * 8, wl);
-            else small_obs_store_row<true>(bsx_at_off(op, iu * (uint32_t)(numel * 4)), o, numel);
+        } else {
+          bsx_emit_at<LOG, NOISE, F64, MT, BSX_OUT_SCALARS.rollout>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
+          if (rows_via_lds) {
+            bsx_f4* w4 = reinterpret_cast<bsx_f4*>(a.out.observation + (oi - wl) * (int64_t)numel);
+            small_obs_store_rows_wave<true>([=](int c) { return w4 + c; }, o, numel, s_rows + (threadIdx.x - wl) * 8, wl);
           } else {
-            if (rows_via_lds) small_obs_store_rows_wave<true>(a.out.observation + (oi - wl) * (int64_t)numel, o, numel, s_rows + (threadIdx.x - wl) * 8, wl);
-            else small_obs_store_row<true>(a.out.observation + oi * (int64_t)numel, o, numel);
+            small_obs_store_row<true>(a.out.observation + oi * (int64_t)numel, o, numel);
           }
         }
       }
@@ -508,7 +484,7 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
         float o[Env::HEAD];
         const bsx_bit_sink sink{wplanes, (int)wstride, (uint32_t)(wl * numel + Env::HEAD)};
         type = Env::template step<LOG, MT, true>(a, i, oi, lane, step0 + (uint64_t)t, o, reward, &sink);
-        bsx_emit_at<LOG, NOISE, F64, MT, (ROLLOUT ? BSX_POLICY_R(1) : BSX_POLICY_E(1))>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
+        bsx_emit_at<LOG, NOISE, F64, MT, bsx_policy(BSX_OUT_SCALARS, ROLLOUT)>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
         float* __restrict__ heads = reinterpret_cast<float*>(a.rows + (uint64_t)R::PLANES * (uint64_t)a.row_plane_words);
         uint32_t head_bits = 0u;
 #pragma unroll
@@ -540,10 +516,8 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
       if (mine) {
         double reward = 0.0;
         float o[8];
-        BSX_LIFE_AFTER_S(2, (uint32_t)step0);                   // the argument slot and the call counter have arrived
         type = Env::template step<LOG, MT>(a, i, oi, lane, step0 + (uint64_t)t, o, reward);
-        BSX_LIFE_AFTER_V(4, type);                              // loads + arithmetic (+ the state stores issued)
-        bsx_emit_at<LOG, NOISE, F64, MT, (ROLLOUT ? BSX_POLICY_R(1) : BSX_POLICY_E(1))>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
+        bsx_emit_at<LOG, NOISE, F64, MT, bsx_policy(BSX_OUT_SCALARS, ROLLOUT)>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
         // (row-per-lane stores also in a big launch: staging the rows like the fused rollout does left the eager step
         // where it was — 17.5 / 17.5 vs 18.0 / 17.4 us at 2^20 lanes — and cost 4 % at 2^18,
         // profiles/r03/ab_eager_rows_via_lds.log: one memory round trip per launch bounds it, not the write requests;
@@ -560,7 +534,8 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
             float* s_rows_e = s_obs;                                // dynamic LDS: small_obs_lds() reserves 256 rows x 8 floats
             const int wl_e = (int)(threadIdx.x & 63u);
             if (i - wl_e + 64 <= B) {                              // (uniform per wave: all 64 lanes are in range)
-              small_obs_store_rows_wave<false>(a.out.observation + (oi - wl_e) * (int64_t)numel, o, numel, s_rows_e + (threadIdx.x - wl_e) * 8, wl_e);
+              bsx_f4* w4 = reinterpret_cast<bsx_f4*>(a.out.observation + (oi - wl_e) * (int64_t)numel);
+              small_obs_store_rows_wave<false>([=](int c) { return w4 + c; }, o, numel, s_rows_e + (threadIdx.x - wl_e) * 8, wl_e);
               staged = true;
             }
           }
@@ -602,7 +577,7 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
         float head[HEAD];
         const bsx_bit_sink sink{planes, stride, (uint32_t)((int)threadIdx.x * numel + HEAD), s_tf};
         type = Env::template step<LOG, MT, true>(a, i, oi, lane, step0 + (uint64_t)t, head, reward, &sink);
-        bsx_emit_at<LOG, NOISE, F64, MT, (ROLLOUT ? BSX_POLICY_R(1) : BSX_POLICY_E(1))>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
+        bsx_emit_at<LOG, NOISE, F64, MT, bsx_policy(BSX_OUT_SCALARS, ROLLOUT)>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
 #pragma unroll
         for (int k = 0; k < HEAD; ++k) s_head[threadIdx.x * HEAD + k] = head[k];
         if (t == 0) {
@@ -650,7 +625,7 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
           q.z = (hm & 4u) ? h2 : q.z;
           q.w = (hm & 8u) ? h3 : q.w;
         }
-        bsx_st<(ROLLOUT ? BSX_POLICY_R(32) : BSX_POLICY_E(32))>(&t4[ch], q);
+        bsx_st<bsx_policy(BSX_OUT_TILE, ROLLOUT)>(&t4[ch], q);
       }
       // elements beyond the 16-byte chunks (an unaligned [t] slice, or the < 4 floats at the end of an odd tile)
       for (int f = (n_chunks << 2) + (int)threadIdx.x; f < total; f += BSX_BLOCK) {
@@ -665,9 +640,7 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
       }
     }
   }
-  BSX_LIFE(5);
   bsx_final_barrier();
-  BSX_LIFE(6);
   bsx_flush_counts(a.ctl, s_cnt, block_id);
 }
 
@@ -718,7 +691,7 @@ __global__ void __launch_bounds__(BSX_BLOCK) small_obs_eager2_kernel(const typen
       double reward = 0.0;
       float o[8];
       type[h] = Env::template core<0, 0, false, false, false, V>(a, rg[h], act[h], i[h], a.ctl.lane_offset + (uint64_t)i[h], step, o, reward);
-      bsx_emit_at<0, 0, false, -1, BSX_POLICY_E(1)>(a.ctl, a.out, i[h], i[h], a.ctl.lane_offset + (uint64_t)i[h], step, type[h], reward);
+      bsx_emit_at<0, 0, false, -1, BSX_OUT_SCALARS.eager>(a.ctl, a.out, i[h], i[h], a.ctl.lane_offset + (uint64_t)i[h], step, type[h], reward);
       small_obs_store_row<false>(a.out.observation + i[h] * (int64_t)numel, o, numel);
       Env::store(a, i[h], rg[h]);
     }
@@ -1076,10 +1049,6 @@ struct bandit_env : small_regs_defaults {
   }
 };
 
-// the chains' step(): the action loaded beside the state word (1) or where the episode needs it (0)
-#ifndef BSX_EARLY_ACTION
-#define BSX_EARLY_ACTION 1
-#endif
 // The time fraction 1 - t / L of the chains' rows (memory_chain.py:64, umbrella_chain.py:64): from the workgroup's LDS
 // table where the PACKED path staged one (bsx_bit_sink::tf), else the f64 division itself.  Evaluated ONCE per step(),
 // before the reset / step paths part ways.
@@ -1212,7 +1181,7 @@ struct memory_chain_env {
   __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t lane, uint64_t step, float* o, double& reward,
                              const Sink* sink = nullptr) {
     int32_t st = a.state[i];
-    const int act = BSX_EARLY_ACTION && !a.ctl.force_reset ? bsx_action(a.ctl, a.action, oi, step) : 0;   // (see umbrella_chain_env::step)
+    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, oi, step);   // (see umbrella_chain_env::step)
     int t = st & 0xFFFFF, query = (st >> 20) & 0xFF;
     uint64_t ctx = a.context[i];
     const bool resets = a.ctl.force_reset || (st & MC_RESET_BIT);
@@ -1244,7 +1213,7 @@ struct memory_chain_env {
     // (the episode's one bsuite_info update: a no-return atomic when episodes are long, i.e. when only a few lanes of a
     // wave end on a given call — bsx_info_add)
     const bool quiet = a.L >= 8 && bsx_info_quiet<LOG>(a.ctl);
-    if ((BSX_EARLY_ACTION ? act : bsx_action(a.ctl, a.action, oi, step)) == (int)((ctx >> query) & 1ull)) { reward = 1.0; bsx_info_add(quiet, &a.info[i], 1.0); }   // :83-85
+    if (act == (int)((ctx >> query) & 1ull)) { reward = 1.0; bsx_info_add(quiet, &a.info[i], 1.0); }   // :83-85
     else { reward = -1.0; bsx_info_add(quiet, &a.info[a.ctl.n_lanes + i], 2.0); }   // :86-88
     a.state[i] = t | (query << 20) | MC_RESET_BIT;
     return BSX_LAST;
@@ -1301,7 +1270,7 @@ struct umbrella_chain_env {
     // (the action matters on the episode's first step only, but which lanes are there is known when the state word has
     // arrived: loaded now, beside it, not in a second dependent round trip — in any real batch every wave holds such a
     // lane, and the line is fetched for it anyway)
-    const int act = BSX_EARLY_ACTION && !a.ctl.force_reset ? bsx_action(a.ctl, a.action, oi, step) : 0;
+    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, oi, step);
     int t = st & 0xFFFFF, need = (st >> 20) & 1, has = (st >> 21) & 1;
     bsx_draws d;
     bsx_draws_begin<MT>(&d, a.ctl, i, lane, step);
@@ -1320,7 +1289,7 @@ struct umbrella_chain_env {
       return BSX_FIRST;
     }
     t += 1;                                                     // :69
-    if (t == 1) has = ((BSX_EARLY_ACTION ? act : bsx_action(a.ctl, a.action, oi, step)) == 1);   // :71-72 (action_spec: {0,1})
+    if (t == 1) has = (act == 1);   // :71-72 (action_spec: {0,1})
     int type;
     if (t == a.L) {                                             // :74-81
       if (has == need) reward = 1.0;

@@ -55,12 +55,10 @@ __device__ __forceinline__ void sweep_phase0_body(const uint8_t* __restrict__ ta
                                                   const uint32_t block, const uint32_t n_blocks, float* s_obs,
                                                   unsigned int* s_cnt, deep_sea_fam::shared& s_ds, catch_fam::shared& s_ca,
                                                   int32_t* s_tile_state, const uint32_t ticket_index = 0xFFFFFFFFu) {
-  BSX_LIFE(0);
   const bsx_group_slot w = bsx_group_find(gi, (int)block);
   const int tag = w.tag >= 0 ? w.tag : tags[w.seg];  // uniform per workgroup
   const uint32_t blk = w.block;
   const uint8_t* slot = table + (size_t)w.seg * BSX_MIXED_ADV_STRIDE;
-  BSX_LIFE_AFTER_S(1, tag);                          // the map entry has arrived
 #define SWEEP_SMALL_CASE(FAM, ENV) \
   case FAM: small_obs_group_body<ENV, 0, true>(*reinterpret_cast<const ENV::args*>(slot), blk, s_obs, s_cnt); break;
   switch (tag) {
@@ -116,7 +114,6 @@ __device__ __forceinline__ void sweep_phase0_body(const uint8_t* __restrict__ ta
       }
     }
   }
-  BSX_LIFE(7);
 }
 
 // block_base: the launch runs the workgroups [block_base, block_base + gridDim.x) of the group's phase-0 grid (the split
@@ -140,12 +137,6 @@ __global__ void __launch_bounds__(BSX_BLOCK) sweep_phase0_kernel(
 }
 
 int bsx_sweep_launch_phase0(bsx_group* g, hipStream_t st) {
-#ifdef BSX_TRACE_LIFE
-  {
-    uint64_t* life = g->trace != nullptr ? g->trace + 3 * (size_t)g->total_blocks : nullptr;   // bsx_group_trace: 11 words per workgroup
-    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(bsx_life_trace_ptr), &life, sizeof(life), 0, hipMemcpyHostToDevice, st);
-  }
-#endif
   sweep_phase0_kernel<<<dim3((unsigned)g->total_blocks), dim3(BSX_BLOCK), g->lds_bytes, st>>>(
       (const uint8_t*)g->d_args, g->d_tags, g->index1(), g->shared_counter, g->d_ticket, g->trace, 0u);
   return (int)hipGetLastError();
@@ -156,10 +147,11 @@ int bsx_sweep_launch_phase0(bsx_group* g, hipStream_t st) {
 // hold the same segments with the two-kernel families' state columns swapped (bsx_call_t.state_alt) and
 // their own TimeStep buffers, so nothing in the launch depends on anything else in it: the stream reads the
 // column phase 0 of step s wrote in the previous launch, phase 0 of step s+1 reads it too and writes the
-// other one.  The latency-bound phase 0 (~26 us alone) hides beside the ~140 us store stream.
+// other one.  The latency-bound phase 0 (~26 us alone) hides beside the ~140 us store stream.  The phase-0 workgroups come
+// first in the grid (bsx_pipe_role_of, place 0: measured best).
 __global__ void __launch_bounds__(BSX_BLOCK) sweep_pipelined_kernel(
     const uint8_t* __restrict__ adv_table, const int32_t* __restrict__ adv_tags, const bsx_group_index adv_gi,
-    uint64_t* counter, uint32_t* ticket, const uint32_t adv_blocks, const uint32_t place,
+    uint64_t* counter, uint32_t* ticket, const uint32_t adv_blocks,
     const uint8_t* __restrict__ str_table, const int32_t* __restrict__ str_tags, const bsx_group_index str_gi) {
   extern __shared__ __attribute__((aligned(16))) float s_obs[];
   __shared__ unsigned int s_cnt[2];
@@ -167,7 +159,7 @@ __global__ void __launch_bounds__(BSX_BLOCK) sweep_pipelined_kernel(
   __shared__ catch_fam::shared s_ca;
   __shared__ float s_lut[MNIST_LUT_FLOATS];
   __shared__ int32_t s_tile_state[BSX_BLOCK];
-  const bsx_pipe_role r = bsx_pipe_role_of(blockIdx.x, gridDim.x, adv_blocks, place);   // uniform per workgroup
+  const bsx_pipe_role r = bsx_pipe_role_of(blockIdx.x, gridDim.x, adv_blocks, 0u);   // uniform per workgroup
   if (r.adv) sweep_phase0_body(adv_table, adv_tags, adv_gi, counter, ticket, r.index, adv_blocks, s_obs, s_cnt, s_ds, s_ca, s_tile_state);
   else pair_mixed_stream_body(str_table, str_tags, str_gi, r.index, s_lut);
 }
@@ -175,10 +167,9 @@ __global__ void __launch_bounds__(BSX_BLOCK) sweep_pipelined_kernel(
 int bsx_sweep_launch_pipelined(bsx_group* streams_of, bsx_group* advances_of, hipStream_t st) {
   const uint64_t blocks = (uint64_t)advances_of->total_blocks + (uint64_t)streams_of->total_blocks2;
   if (blocks == 0 || blocks > 0x7FFFFFFFull) return BSX_EINVAL;
-  static const int place = bsx_env_int("BSX_PIPELINED_PLACE", 0);       // bsx_pipe_role_of: first (measured best)
   sweep_pipelined_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), advances_of->lds_bytes, st>>>(
       (const uint8_t*)advances_of->d_args, advances_of->d_tags, advances_of->index1(), advances_of->shared_counter,
-      advances_of->d_ticket, (uint32_t)advances_of->total_blocks, (uint32_t)place, (const uint8_t*)streams_of->d_args2, streams_of->d_tags,
+      advances_of->d_ticket, (uint32_t)advances_of->total_blocks, (const uint8_t*)streams_of->d_args2, streams_of->d_tags,
       streams_of->index2());
   return (int)hipGetLastError();
 }
@@ -201,13 +192,9 @@ int bsx_sweep_launch_pipelined(bsx_group* streams_of, bsx_group* advances_of, hi
 // (profiles/r05/ab_sweep_split_point*.log: 164.2 us per sweep step with no top-up, 163.0 with 1200 workgroups, 162.0 with 1500,
 // 163.2 with 1800, noise from 2200 = slots x 1.07 up to 3000 = slots x 1.46; with ALL of phase 0 in launch 1 168).  Derived
 // per group and device, not a constant: another mix of families (more LDS per workgroup = fewer slots) or a part with fewer
-// CUs gets its own round.  -DBSX_SPLIT_ROUND_DEFAULT=<n> / BSX_SPLIT_ROUND (tuning build) pin it; 0 = the lane advance only.
+// CUs gets its own round.  BSX_SPLIT_ROUND (tuning build) pins it; 0 = the lane advance only.
 static int64_t sweep_split_round(bsx_group* g) {
-#ifdef BSX_SPLIT_ROUND_DEFAULT
-  static const int pinned = bsx_env_int("BSX_SPLIT_ROUND", BSX_SPLIT_ROUND_DEFAULT);
-#else
   static const int pinned = bsx_env_int("BSX_SPLIT_ROUND", -1);
-#endif
   if (pinned >= 0) return pinned;
   if (g->split_round >= 0) return g->split_round;
   int dev = 0, cus = 0, per_cu = 0;
@@ -245,9 +232,8 @@ int bsx_sweep_launch_split(bsx_group* g, hipStream_t st) {
   const uint64_t blocks = (uint64_t)split + (uint64_t)g->total_blocks2;
   if (blocks == 0) return (int)hipGetLastError();
   if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
-  static const int place = bsx_env_int("BSX_SPLIT_PLACE", 0);            // bsx_pipe_role_of: 0 = the phase-0 workgroups first
   sweep_pipelined_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), g->lds_bytes, st>>>(
-      (const uint8_t*)g->d_args, g->d_tags, g->index1(), g->shared_counter, g->d_ticket, (uint32_t)split, (uint32_t)place,
+      (const uint8_t*)g->d_args, g->d_tags, g->index1(), g->shared_counter, g->d_ticket, (uint32_t)split,
       (const uint8_t*)g->d_args2, g->d_tags, g->index2());
   return (int)hipGetLastError();
 }

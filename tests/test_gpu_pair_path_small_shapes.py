@@ -101,7 +101,7 @@ def test_two_lanes_per_thread_eager_step_at_small_shapes():
 @pytest.mark.timeout(900)
 def test_split_sweep_step_with_a_topped_up_first_launch():
   """bsx_group_step_split tops launch 1 up with small-observation workgroups when phase 0 is more than one dispatch round
-  (BSX_SPLIT_ROUND_DEFAULT workgroups, csrc/sweep_mixed.hip) — in-process only the 2^20-lane tests get there
+  (sweep_split_round workgroups, csrc/sweep_mixed.hip) — in-process only the 2^20-lane tests get there
   (test_gpu_benched_sizes.py).  The sweep-group tests once more through the tuning build with the round at 3 and 20
   workgroups: launch 1 = the lane advance alone / + a few / + all of the small segments' workgroups, the call counter
   bumped from whichever launch retires the last of them."""

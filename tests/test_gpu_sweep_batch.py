@@ -318,7 +318,7 @@ def test_eager_and_grouped_steps_alternate_on_one_counter():
 def test_grouped_mnist_on_a_dataset_beyond_l2_equals_standalone_envs(tmp_path, mix_all):
   """An image table larger than the chip's 32 MiB of L2 (the real MNIST's class) switches the mnist observation stream to
   non-temporal stores (csrc/mnist.hip: `mnist_observe_args.nt`, per segment) — stand-alone, inside the whole-sweep group
-  (6 KiB-runs per wave) and inside a per-family pair group: same TimeSteps and bsuite_info as the stand-alone environments."""
+  (4 KiB-runs per wave) and inside a per-family pair group: same TimeSteps and bsuite_info as the stand-alone environments."""
   from bsuite_amd.utils import datasets
   rng = np.random.default_rng(4)
   imgs = rng.integers(0, 256, size=(43000, 28, 28), dtype=np.uint8)

@@ -30,20 +30,39 @@ def waves_per_simd(vgprs):
   return max(1, min(8, 512 // max(8, (vgprs + 7) // 8 * 8)))
 
 
+def _code_objects(lib, d):
+  """Paths of the gfx950 code objects of `lib`, one per translation unit, unbundled into directory `d`."""
+  fat = os.path.join(d, 'fat.bin')
+  subprocess.run([os.path.join(LLVM, 'llvm-objcopy'), '--dump-section', f'.hip_fatbin={fat}', lib, os.path.join(d, 'copy.so')], check=True)
+  data = open(fat, 'rb').read()
+  starts = [m.start() for m in re.finditer(b'__CLANG_OFFLOAD_BUNDLE__', data)]
+  cos = []
+  for k, p in enumerate(starts):
+    bundle, co = os.path.join(d, f'b{k}.bin'), os.path.join(d, f'b{k}.co')
+    with open(bundle, 'wb') as f:
+      f.write(data[p:starts[k + 1] if k + 1 < len(starts) else len(data)])
+    subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o', f'--input={bundle}',
+                    f'--targets={TARGET}', f'--output={co}'], check=True)
+    cos.append(co)
+  return cos
+
+
+def instructions(lib):
+  """Every instruction of `lib`'s code objects as llvm-objdump disassembles it (operands, no encoding), in order."""
+  out = []
+  with tempfile.TemporaryDirectory(prefix='bsx_co_', dir='/tmp') as d:
+    for co in _code_objects(lib, d):
+      text = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn', '--mcpu=gfx950', co],
+                            stdout=subprocess.PIPE, text=True, check=True).stdout
+      out += [l.split('//')[0].strip() for l in text.split('\n') if l.startswith(('\t', ' ')) and l.strip()]
+  return out
+
+
 def kernels(lib):
   """[{name (demangled), symbol, vgpr_count, ..., waves_per_simd}] for every kernel of `lib`."""
   out = []
   with tempfile.TemporaryDirectory(prefix='bsx_co_', dir='/tmp') as d:
-    fat = os.path.join(d, 'fat.bin')
-    subprocess.run([os.path.join(LLVM, 'llvm-objcopy'), '--dump-section', f'.hip_fatbin={fat}', lib, os.path.join(d, 'copy.so')], check=True)
-    data = open(fat, 'rb').read()
-    starts = [m.start() for m in re.finditer(b'__CLANG_OFFLOAD_BUNDLE__', data)]
-    for k, p in enumerate(starts):
-      bundle, co = os.path.join(d, f'b{k}.bin'), os.path.join(d, f'b{k}.co')
-      with open(bundle, 'wb') as f:
-        f.write(data[p:starts[k + 1] if k + 1 < len(starts) else len(data)])
-      subprocess.run([os.path.join(LLVM, 'clang-offload-bundler'), '--unbundle', '--type=o', f'--input={bundle}',
-                      f'--targets={TARGET}', f'--output={co}'], check=True)
+    for co in _code_objects(lib, d):
       notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', co], stdout=subprocess.PIPE, text=True, check=True).stdout
       for block in notes.split('  - .agpr_count:')[1:]:
         block = '.agpr_count:' + block
