@@ -160,6 +160,7 @@ lib = _load()
 _P = ctypes.c_void_p
 _SIGS = {
     'bsx_abi_version': ([], ctypes.c_int),
+    'bsx_observation_dtypes': ([ctypes.c_int32], ctypes.c_int),
     'bsx_row_scratch_bytes': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64], ctypes.c_int64),
     'bsx_bsuite_info': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P],
                         ctypes.c_int),
@@ -222,6 +223,10 @@ if MISSING:
   raise NativeLibraryError(f'{SO_PATH} does not export {MISSING}; rebuild with `python -m bsuite_amd.build --force`')
 ABI_VERSION = 12
 CALL_STATE_TAGGED = 1   # BSX_CALL_STATE_TAGGED
+# bsx_call_t.flags field of the observation element type (BSX_CALL_OBS_*): code << CALL_OBS_SHIFT, code 0 = float32
+CALL_OBS_SHIFT = 1
+CALL_OBS_MASK = 3 << CALL_OBS_SHIFT
+CALL_OBS_F32, CALL_OBS_U8, CALL_OBS_F16, CALL_OBS_BF16 = (k << CALL_OBS_SHIFT for k in range(4))
 if lib.bsx_abi_version() != ABI_VERSION:
   raise NativeLibraryError('ABI version mismatch between bsuite_amd/_native.py and libbsuite_amd.so')
 

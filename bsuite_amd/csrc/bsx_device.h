@@ -821,4 +821,113 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_hot_stream_tiny_kernel(float* _
   obs[F] = (ha == r || hb == r) ? 1.0f : 0.0f;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Narrow observation stream (bsx_call_t.flags & BSX_CALL_OBS_MASK): the same flat run of 16-byte chunks as
+// bsx_hot_stream_body, but a chunk holds N = 16 / E elements of E bytes (uint8: E = 1; float16 / bfloat16: E = 2).
+// A chunk starts as four zero dwords and receives the element's "one" bit pattern (`one`: 0x01, 0x3C00 or 0x3F80) at
+// the at most four positions the hot cells of its lanes fall on — two lanes once a row has at least N cells; a
+// lane without hot cell (deep_sea's all-zero terminal board: -1) contributes nothing.  Every whole chunk is ONE
+// 16-byte store: element stores cost many times more per byte (sub-dword stores of the MI355X).
+//
+// The array [n_lanes x cells] starts at `obs` (any E-aligned address: slice t of a rollout lies t*B*cells*E bytes
+// into the buffer): `head` elements up to the first 16-byte boundary, then n_chunks whole chunks, then a tail of
+// fewer than N elements.  Workgroup 0 writes head and tail with element stores.  Boards of fewer than N cells
+// (deep_sea N <= 3, catch below 16 / 8 cells) put several lanes into one chunk and take a slow loop over them.
+template <int E>
+struct bsx_narrow_chunk {                 // the 16 bytes of one chunk as two 64-bit halves
+  uint64_t lo = 0, hi = 0;
+  // sets element p (no-op unless 0 <= p < 16 / E)
+  __device__ __forceinline__ void put(int p, uint32_t one) {
+    if ((unsigned)p >= (unsigned)(16 / E)) return;
+    const uint32_t bit = (uint32_t)p * (8u * E);
+    const uint64_t v = (uint64_t)one << (bit & 63u);
+    if (bit < 64u) lo |= v; else hi |= v;
+  }
+};
+
+template <class HotFn, int E, int K>
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_narrow_stream_kernel(uint8_t* __restrict__ obs,
+                                                                      const int32_t* __restrict__ state,
+                                                                      int64_t n_lanes, uint32_t cells,
+                                                                      uint32_t cells_magic, bsx_div64 dv,
+                                                                      uint32_t head, uint64_t n_chunks,
+                                                                      uint32_t one, HotFn fn) {
+  constexpr int N = 16 / E;
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  const uint64_t total = (uint64_t)n_lanes * cells;
+  if (blockIdx.x == 0 && threadIdx.x < 2 * N) {        // ragged head (threads 0..N-1) and tail (N..2N-1)
+    const uint64_t e = threadIdx.x < N ? (uint64_t)threadIdx.x : head + n_chunks * N + (threadIdx.x - N);
+    if (threadIdx.x < N ? e < head : e < total) {
+      const uint64_t l = e / cells;
+      const int r = (int)(e - l * cells);
+      int ha, hb;
+      fn(state[l], ha, hb);
+      const uint32_t v = (ha == r || hb == r) ? one : 0u;
+      if constexpr (E == 1) obs[e] = (uint8_t)v;
+      else reinterpret_cast<uint16_t*>(obs)[e] = (uint16_t)v;
+    }
+  }
+  const uint64_t c_b = (uint64_t)blockIdx.x * (K * BSX_BLOCK);          // the workgroup's first chunk
+  u4* __restrict__ o4 = reinterpret_cast<u4*>(obs + (uint64_t)head * E) + c_b;
+  if (cells < (uint32_t)N) {                                            // several lanes per chunk: the slow path
+#pragma unroll 1
+    for (int u = 0; u < K; ++u) {
+      const uint32_t c = (threadIdx.x >> 6) * (K * 64) + u * 64 + (threadIdx.x & 63);
+      if (c_b + c >= n_chunks) continue;
+      const uint64_t e0 = head + (c_b + c) * N;
+      uint64_t l = e0 / cells;
+      int base = -(int)(e0 - l * cells);                                // chunk position of lane l's cell 0
+      bsx_narrow_chunk<E> v;
+      for (; base < N && l < (uint64_t)n_lanes; base += (int)cells, ++l) {
+        int ha, hb;
+        fn(state[l], ha, hb);
+        v.put(ha < 0 ? -1 : base + ha, one);
+        v.put(hb < 0 ? -1 : base + hb, one);
+      }
+      u4 w;
+      w.x = (uint32_t)v.lo; w.y = (uint32_t)(v.lo >> 32); w.z = (uint32_t)v.hi; w.w = (uint32_t)(v.hi >> 32);
+      o4[c] = w;
+    }
+    return;
+  }
+  // rows of at least N cells: a chunk touches lane dl and, when it runs over the row's end, lane dl + 1
+  const uint64_t E0 = head + c_b * N;                                   // the workgroup's first element (uniform)
+  const uint64_t lane_b = __umul64hi(E0, dv.m) >> dv.s;
+  const uint32_t r_b = (uint32_t)(E0 - lane_b * cells);
+  const int32_t* __restrict__ st = state + lane_b;
+  const uint64_t lanes_left = (uint64_t)n_lanes - lane_b;
+  uint32_t dl[K];
+  int r0[K];
+  int32_t s0[K], s1[K];
+  bool live[K];
+#pragma unroll
+  for (int u = 0; u < K; ++u) {
+    const uint32_t c = (threadIdx.x >> 6) * (K * 64) + u * 64 + (threadIdx.x & 63);
+    const uint32_t f = r_b + c * N;                                     // < 2^20: the 32-bit magic is exact
+    dl[u] = __umulhi(f, cells_magic);
+    r0[u] = (int)(f - dl[u] * cells);
+    live[u] = c_b + c < n_chunks;
+    s0[u] = live[u] ? st[dl[u]] : 0;
+    s1[u] = (live[u] && (int)cells - r0[u] < N && (uint64_t)dl[u] + 1 < lanes_left) ? st[dl[u] + 1] : 0;
+  }
+#pragma unroll
+  for (int u = 0; u < K; ++u) {
+    if (!live[u]) continue;
+    bsx_narrow_chunk<E> v;
+    int ha, hb;
+    fn(s0[u], ha, hb);
+    v.put(ha < 0 ? -1 : ha - r0[u], one);
+    v.put(hb < 0 ? -1 : hb - r0[u], one);
+    const int over = (int)cells - r0[u];                                // elements >= over belong to lane dl + 1
+    if (over < N) {
+      fn(s1[u], ha, hb);
+      v.put(ha < 0 ? -1 : ha + over, one);
+      v.put(hb < 0 ? -1 : hb + over, one);
+    }
+    u4 w;
+    w.x = (uint32_t)v.lo; w.y = (uint32_t)(v.lo >> 32); w.z = (uint32_t)v.hi; w.w = (uint32_t)(v.hi >> 32);
+    o4[(threadIdx.x >> 6) * (K * 64) + u * 64 + (threadIdx.x & 63)] = w;
+  }
+}
+
 #endif  // BSX_DEVICE_H_

@@ -9,10 +9,15 @@
 
 #include "bsx_device.h"
 
+// Observation element code of a call (bsx_call_t.flags, BSX_CALL_OBS_*): 0 float32, 1 uint8, 2 float16, 3 bfloat16.
+static inline int bsx_call_obs(const bsx_call_t* call) { return (call->flags & BSX_CALL_OBS_MASK) >> BSX_CALL_OBS_SHIFT; }
+
+// delta_ok / narrow_ok: the family has the delta observation mode (obs_paint) / the narrow observation codes.
 static inline int bsx_check_call(const bsx_call_t* call, const void* action, const bsx_timestep_t& out,
-                                 bool delta_ok = false) {
+                                 bool delta_ok = false, bool narrow_ok = false) {
   if (call == nullptr) return BSX_ENULL;
   if (call->obs_paint != nullptr && (!delta_ok || call->n_steps > 1)) return BSX_EMODE;
+  if (bsx_call_obs(call) != 0 && (!narrow_ok || call->obs_paint != nullptr)) return BSX_EMODE;
   if (call->n_lanes < 0 || call->n_lanes > ((int64_t)1 << 40)) return BSX_EINVAL;
   if (call->n_lanes == 0) return 0;
   if (out.reward == nullptr || out.discount == nullptr || out.step_type == nullptr ||
@@ -150,6 +155,33 @@ static inline int bsx_launch_hot_stream(float* obs, const int32_t* state, int64_
   return 0;
 }
 
+// Launches the narrow observation stream (bsx_narrow_stream_kernel) of one step: `obs` -> [n_lanes x cells] elements of
+// observation code `code` (1..3), at any element-aligned address.
+template <class HotFn, int K>
+static inline int bsx_launch_narrow_stream(void* obs, const int32_t* state, int64_t n_lanes, uint32_t cells, int code,
+                                           HotFn fn, hipStream_t st) {
+  static const uint32_t one[4] = {0u, 0x01u, 0x3C00u, 0x3F80u};      // the element's 1.0 (index: observation code)
+  const int E = code == 1 ? 1 : 2, N = 16 / E;
+  const uint64_t total = (uint64_t)n_lanes * cells;
+  uint64_t head = ((16u - (reinterpret_cast<uintptr_t>(obs) & 15u)) & 15u) / (uint64_t)E;
+  if (head > total) head = total;
+  const uint64_t n_chunks = (total - head) / (uint64_t)N;
+  const uint64_t per_block = (uint64_t)K * BSX_BLOCK;
+  const uint64_t blocks = n_chunks == 0 ? 1 : (n_chunks + per_block - 1) / per_block;   // workgroup 0 writes head and tail
+  if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
+  const bool wide = cells >= (uint32_t)N;                   // the kernel's fast path (bsx_make_div64 needs cells >= 4)
+  const uint32_t magic = wide ? bsx_div_magic(cells) : 0u;
+  const bsx_div64 dv = wide ? bsx_make_div64(cells) : bsx_div64{0, 0};
+  const dim3 grid((unsigned)blocks), block(BSX_BLOCK);
+  if (E == 1)
+    bsx_narrow_stream_kernel<HotFn, 1, K><<<grid, block, 0, st>>>((uint8_t*)obs, state, n_lanes, cells, magic, dv,
+                                                                   (uint32_t)head, n_chunks, one[code], fn);
+  else
+    bsx_narrow_stream_kernel<HotFn, 2, K><<<grid, block, 0, st>>>((uint8_t*)obs, state, n_lanes, cells, magic, dv,
+                                                                   (uint32_t)head, n_chunks, one[code], fn);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Grouped launch (bsx_group_t): host-side container.  Each family file fills `args`/`args2` (its
 // kernel argument structs, one per segment) and the per-segment block counts, and installs `launch`.
@@ -273,6 +305,21 @@ static int bsx_pair_call(const typename Fam::args& a0, const bsx_call_t* call, c
     s.out.observation = out.observation + off * (int64_t)cells;
     return s;
   };
+  // Narrow observations (BSX_CALL_OBS_*): lane advance + narrow store stream per step, at every batch size.  Taken before
+  // every size rule below: the fused tiles, the pipelined rollout and their byte thresholds are float32-only.
+  const int obs_code = bsx_call_obs(call);
+  if (obs_code != 0) {
+    const int64_t slice_bytes = B * (int64_t)cells * (obs_code == 1 ? 1 : 2);
+    int rc = 0;
+    for (int t = 0; t < T && rc == 0; ++t) {
+      typename Fam::args s = at(t);
+      void* obs_t = (uint8_t*)out.observation + (int64_t)t * slice_bytes;
+      s.out.observation = (float*)obs_t;                  // (the advance never touches the observation)
+      rc = bsx_launch_advance<Fam>(s, st);
+      if (rc == 0) rc = bsx_launch_narrow_stream<HotFn, K>(obs_t, state, B, cells, obs_code, fn, st);
+    }
+    return rc != 0 ? rc : bsx_launch_status();
+  }
   const uint32_t magic = bsx_div_magic(cells);
   static const int place = bsx_env_int("BSX_PIPELINED_PLACE", 0);     // bsx_pipe_role_of: first (measured best)
   // the fused launch uses the 16-byte store stream: every [t] slice must start on a 16-byte boundary

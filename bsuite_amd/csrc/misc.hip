@@ -7,6 +7,11 @@
 
 extern "C" int bsx_abi_version(void) { return BSX_ABI_VERSION; }
 
+extern "C" int bsx_observation_dtypes(int32_t family) {
+  if (family == BSX_FAM_DEEP_SEA || family == BSX_FAM_CATCH) return 0xF;   // float32, uint8, float16, bfloat16
+  return (family >= 0 && family <= BSX_FAM_SWEEP_MIXED) ? 0x1 : 0;
+}
+
 extern "C" const char* bsx_strerror(int code) {
   switch (code) {
     case 0: return "ok";
@@ -14,7 +19,7 @@ extern "C" const char* bsx_strerror(int code) {
     case BSX_ENULL: return "required pointer is NULL";
     case BSX_EALIGN: return "observation buffer (or row scratch) is not 16-byte aligned";
     case BSX_ERANGE: return "parameter outside the supported range of this family";
-    case BSX_EMODE: return "combination not available (randn in MT19937-exact mode; obs_paint with a rollout, a group or a family without a board)";
+    case BSX_EMODE: return "combination not available (randn in MT19937-exact mode; obs_paint with a rollout, a group or a family without a board; a narrow observation type outside a single deep_sea / catch call or with obs_paint)";
     case BSX_ENOMEM: return "host allocation failed";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown bsx error";
   }

@@ -45,6 +45,13 @@ if _current_raw_stream is None:
 _current_device = getattr(torch._C, '_cuda_getDevice', None) or torch.cuda.current_device   # pylint: disable=protected-access
 
 
+# observation_dtype -> the element code of bsx_call_t.flags (BSX_CALL_OBS_*)
+_OBS_CODES = {torch.float32: 0, torch.uint8: 1, torch.float16: 2, torch.bfloat16: 3}
+_OBS_NAMES = {'float32': torch.float32, 'uint8': torch.uint8, 'float16': torch.float16, 'bfloat16': torch.bfloat16}
+_OBS_SPEC_DTYPES = {torch.float32: np.float32, torch.uint8: np.uint8, torch.float16: np.float16,
+                    torch.bfloat16: np.float32}     # numpy has no bfloat16: see Environment.observation_spec
+
+
 def _resolve_seed(seed: Optional[int]) -> int:
   """seed=None means fresh OS entropy, as np.random.RandomState(None) does in the reference."""
   if seed is None:
@@ -60,6 +67,7 @@ class Environment(dm_env.EnvironmentBase):
 
   # Subclass constants.
   _supports_delta = False  # families whose observation is a board with <= 2 hot cells
+  _supports_narrow_obs = False  # families whose observations are all 0/1: observation_dtype may be narrower than float32
   _pipelined_rollout = False  # two-kernel families whose rollouts are software-pipelined (state_alt)
   _state_alt = None
   scalar_host_buffers = True   # scalar view: TimeStep / action buffers in pinned host memory mapped into the device (class
@@ -91,7 +99,7 @@ class Environment(dm_env.EnvironmentBase):
 
   def __init__(self, obs_shape, num_actions, *, seed=None, batch=None, device=None,
                lane_offset=0, num_buffers=2, device_step_counter=False, shared_step_counter=None,
-               rng='philox', observation_mode='dense', obs_allocator=None):
+               rng='philox', observation_mode='dense', obs_allocator=None, observation_dtype=torch.float32):
     self._scalar = batch is None
     self._scalar_last_type = None    # scalar view: step_type of the previous TimeStep (DiscountingChain._check_scalar_action)
     self._batch = 1 if batch is None else int(batch)
@@ -129,6 +137,23 @@ class Environment(dm_env.EnvironmentBase):
     if observation_mode == 'delta' and not self._supports_delta:
       raise ValueError(f'{type(self).__name__} has no delta observation mode (its observations are small and dense)')
     self._delta = observation_mode == 'delta'
+    # observation_dtype (deep_sea, catch): the element type the engine writes its observations in — float32, or uint8 /
+    # float16 / bfloat16, which hold the boards' 0.0 and 1.0 exactly in a quarter / half of the bytes.  Batched, dense,
+    # single environments only; checked here, before any GPU use.
+    dt = _OBS_NAMES.get(observation_dtype, observation_dtype) if isinstance(observation_dtype, str) else observation_dtype
+    if dt not in _OBS_CODES:
+      raise ValueError(f'observation_dtype must be one of {sorted(_OBS_NAMES)} (or the torch dtypes), got {observation_dtype!r}')
+    if dt != torch.float32:
+      if not self._supports_narrow_obs:
+        raise ValueError(f'{type(self).__name__} writes float32 observations only (observation_dtype={observation_dtype!r})')
+      if self._scalar:
+        raise ValueError('observation_dtype other than float32 needs the batched view (batch=B)')
+      if self._delta:
+        raise ValueError("observation_dtype other than float32 needs observation_mode='dense'")
+      if obs_allocator is not None:
+        raise ValueError('observation_dtype other than float32 is not available in SweepBatch (float32 arenas)')
+    self._obs_dtype = dt
+    self._obs_flags = _OBS_CODES[dt] << _native.CALL_OBS_SHIFT
     if rng not in ('philox', 'mt19937'):
       raise ValueError("rng must be 'philox' or 'mt19937'")
     self._rng_mode = rng
@@ -163,6 +188,11 @@ class Environment(dm_env.EnvironmentBase):
   @property
   def seed(self) -> int:
     return self._seed
+
+  @property
+  def observation_dtype(self) -> torch.dtype:
+    """The torch dtype of the observation tensors step() / reset() / rollout() return."""
+    return self._obs_dtype
 
   @property
   def lane_offset(self) -> int:
@@ -234,6 +264,8 @@ class Environment(dm_env.EnvironmentBase):
       raise ValueError('grouped launches need device_step_counter / shared_step_counter')
     if self._delta:
       raise ValueError("grouped launches write dense observations; use observation_mode='dense'")
+    if self._obs_flags:
+      raise ValueError('grouped launches write float32 observations; use observation_dtype=torch.float32')
     call = self._call_desc
     call.force_reset, call.n_steps = 0, 0
     kind, param, wseed, param2 = self._wrap
@@ -347,7 +379,7 @@ class Environment(dm_env.EnvironmentBase):
             step_type=torch.empty(B, dtype=torch.int8, **place),
             observation=(self._obs_allocator((B,) + self._obs_shape)
                          if (self._obs_allocator is not None and not self._scalar and not self._delta) else
-                         (torch.zeros if self._delta else torch.empty)((B,) + self._obs_shape, dtype=torch.float32, **place)))
+                         (torch.zeros if self._delta else torch.empty)((B,) + self._obs_shape, dtype=self._obs_dtype, **place)))
         self._out.append(o)
         self._out_ptrs.append(_native.TimeStepPtrs(
             o['reward'].data_ptr(), o['discount'].data_ptr(), o['step_type'].data_ptr(),
@@ -395,6 +427,7 @@ class Environment(dm_env.EnvironmentBase):
     if self._state_tag_bit is not None:
       self._tag_calls = self._shared_step_counter is None
       self._call_desc.flags = _native.CALL_STATE_TAGGED if self._tag_calls else 0
+    self._call_desc.flags |= self._obs_flags
     self._tag_host_count = self._tag_calls and not self._device_step_counter
     self._dev_index = self._device.index
     self._timesteps = None if self._scalar else [
@@ -420,7 +453,7 @@ class Environment(dm_env.EnvironmentBase):
     if self._tag_host_count:                       # (deep_sea with the host-side call count: not while capturing.  The
       # current device IS this environment's here — the redirect at the top of _call — so this asks about the stream the
       # kernels are about to be launched on)
-      call.flags = 0 if torch.cuda.is_current_stream_capturing() else _native.CALL_STATE_TAGGED
+      call.flags = (0 if torch.cuda.is_current_stream_capturing() else _native.CALL_STATE_TAGGED) | self._obs_flags
     if self._wrap is not self._wrap_applied:       # the wrappers install a NEW tuple when they change it
       w = self._call_wrap
       w.kind, w.param, w.seed, w.param2 = self._wrap
@@ -617,7 +650,7 @@ class Environment(dm_env.EnvironmentBase):
       o = dict(reward=torch.empty((T, B), dtype=torch.float32, device=dev),
                discount=torch.empty((T, B), dtype=torch.float32, device=dev),
                step_type=torch.empty((T, B), dtype=torch.int8, device=dev),
-               observation=torch.empty((T, B) + self._obs_shape, dtype=torch.float32, device=dev))
+               observation=torch.empty((T, B) + self._obs_shape, dtype=self._obs_dtype, device=dev))
       cache[T] = (o, _native.TimeStepPtrs(o['reward'].data_ptr(), o['discount'].data_ptr(),
                                           o['step_type'].data_ptr(), o['observation'].data_ptr()))
     out, ptrs = cache[T]
@@ -661,7 +694,13 @@ class Environment(dm_env.EnvironmentBase):
   # ----------------------------------------------------------------------------------------
   # specs / metadata
   def observation_spec(self):
-    return specs.Array(shape=self._obs_shape, dtype=np.float32, name='observation')
+    """Shape and dtype of one lane's observation.  With observation_dtype=torch.bfloat16 the dtype reported is
+    np.float32 (numpy has no bfloat16) while the tensors are bfloat16: every value the spec allows (0.0 and 1.0 for
+    the boards that support narrow types) is exact in it, and `observation_dtype` is the authority."""
+    return specs.Array(shape=self._obs_shape, dtype=self._obs_spec_dtype(), name='observation')
+
+  def _obs_spec_dtype(self):
+    return _OBS_SPEC_DTYPES[self._obs_dtype]
 
   def action_spec(self):
     return specs.DiscreteArray(self._num_actions, name='action')

@@ -42,6 +42,7 @@ class Catch(base.Environment):
 
   _abi_name = 'catch'
   _supports_delta = True
+  _supports_narrow_obs = True
   _pipelined_rollout = True
 
   def _native_args(self, call, action_ptr, out):
@@ -51,7 +52,8 @@ class Catch(base.Environment):
     _ACTIONS[action]  # IndexError exactly where catch.py:84 raises it  pylint: disable=pointless-statement
 
   def observation_spec(self) -> specs.BoundedArray:
-    return specs.BoundedArray(shape=self._obs_shape, dtype=np.float32, name='observation',
+    """A BoundedArray in [0, 1]; for observation_dtype=torch.bfloat16 its dtype is np.float32 (base.Environment.observation_spec)."""
+    return specs.BoundedArray(shape=self._obs_shape, dtype=self._obs_spec_dtype(), name='observation',
                               minimum=0, maximum=1)
 
   def action_spec(self) -> specs.DiscreteArray:

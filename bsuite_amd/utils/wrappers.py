@@ -373,6 +373,9 @@ class ImageObservation(dm_env.EnvironmentBase):
   call with a single kernel launch; the scalar view returns numpy images like the reference."""
 
   def __init__(self, env, shape: Sequence[int], num_buffers: int = 2):
+    if getattr(env, 'observation_dtype', torch.float32) != torch.float32:
+      raise TypeError(f'ImageObservation converts float32 observations; this environment writes {env.observation_dtype} '
+                      '(construct it with observation_dtype=torch.float32)')
     self._env = env
     self._shape = tuple(int(s) for s in shape)
     _image_cfg(self._shape, env.observation_spec().shape)       # validate once, like the first to_image call would

@@ -94,7 +94,8 @@ typedef struct {
   float* reward;        /* [B]                                   */
   float* discount;      /* [B]                                   */
   int8_t* step_type;    /* [B]                                   */
-  float* observation;   /* [B, obs_numel], 16-byte aligned       */
+  float* observation;   /* [B, obs_numel], 16-byte aligned; elements of another type under a narrow
+                           bsx_call_t.flags code (BSX_CALL_OBS_*)                               */
 } bsx_timestep_t;
 
 /* Batched form of the `Logging` wrapper's bookkeeping (bsuite/utils/wrappers.py:85-125): per-lane
@@ -212,6 +213,23 @@ typedef struct {
                                   launch instead of two: the threads of the observation store stream recompute the
                                   transition of the lane whose row they write (deep_sea.hip).  Without the flag:
                                   lane advance + store stream, as in v10.                                      */
+/* Observation element type (a 2-bit field of flags; 0 = float32, the v12 behaviour).  deep_sea and catch boards hold
+ * only 0.0 and 1.0, exact in every narrow type; with a narrow code `out.observation` (still declared float*, still
+ * 16-byte aligned) points to B * obs_numel elements of that type — [T,B,obs_numel] in a rollout, slice t starting
+ * t * B * obs_numel * sizeof(element) bytes in — and the board's ones are written as 0x01, 0x3C00 or 0x3F80.  A
+ * narrow call is lane advance + narrow store stream per step (a rollout: T such pairs).  BSX_EMODE, before any
+ * device work, for any other family, with obs_paint, and in a group (bsx_group_set_*).  Which codes a family accepts:
+ * bsx_observation_dtypes. */
+#define BSX_CALL_OBS_SHIFT 1
+#define BSX_CALL_OBS_MASK (3 << BSX_CALL_OBS_SHIFT)
+#define BSX_CALL_OBS_F32 (0 << BSX_CALL_OBS_SHIFT)
+#define BSX_CALL_OBS_U8 (1 << BSX_CALL_OBS_SHIFT)    /* uint8_t, one = 0x01                 */
+#define BSX_CALL_OBS_F16 (2 << BSX_CALL_OBS_SHIFT)   /* IEEE binary16, one = 0x3C00         */
+#define BSX_CALL_OBS_BF16 (3 << BSX_CALL_OBS_SHIFT)  /* bfloat16, one = 0x3F80              */
+
+/* Bit k set: family `family` (BSX_FAM_*) accepts observation code k (flags field BSX_CALL_OBS_*, k = 0..3): 0xF for
+ * deep_sea and catch, 0x1 (float32 only) for the other families and groups, 0 for an unknown family.  Host only. */
+int bsx_observation_dtypes(int32_t family);
 
 /* A catch segment of a BSX_FAM_SWEEP_MIXED group whose board has at most this many cells and that was set WITHOUT
  * state_alt has its boards written by phase 0 itself (one fused tile per workgroup) and takes no part in the phase-1
