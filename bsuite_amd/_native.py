@@ -169,6 +169,8 @@ _SIGS = {
     'bsx_calib_copy': ([_P, _P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     'bsx_counter_add': ([_P, ctypes.c_uint64, _P], ctypes.c_int),
     'bsx_image_observation': ([ctypes.POINTER(ImageCfg), ctypes.c_int64, _P, _P, _P], ctypes.c_int),
+    'bsx_image_observation_typed': ([ctypes.POINTER(ImageCfg), ctypes.c_int64, _P, ctypes.c_int32, _P, ctypes.c_int32,
+                                     _P], ctypes.c_int),
     'bsx_stream_dump': ([ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64,
                          ctypes.c_int32, ctypes.c_int32, _P, _P, _P], ctypes.c_int),
     'bsx_deep_sea_step': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],

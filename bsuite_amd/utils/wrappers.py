@@ -13,7 +13,8 @@ fused into the kernels' emit epilogue (bsx_logging_t) so that every lane accumul
 the reference wrapper would and snapshots a row at the same log-spaced counts; the Python class
 below keeps the reference constructor and forwards rows to a `logger.write(dict)` object.
 `ImageObservation` / `to_image` (wrappers.py:150-247) run as one store-stream kernel
-over the whole batch (bsx_image_observation, csrc/image.hip).
+over the whole batch (bsx_image_observation_typed, csrc/image.hip), in any of the four observation
+dtypes.
 """
 from typing import Any, Dict, List, Optional, Sequence
 
@@ -334,34 +335,80 @@ def _gaussian_half_kernel(n_in: int, n_out: int):
   return phi[radius:]
 
 
-def to_image(shape: Sequence[int], observation, out: Optional[torch.Tensor] = None, batched=None):
+# element codes of bsx_image_observation_typed (the observation numbering, BSX_CALL_OBS_* >> BSX_CALL_OBS_SHIFT)
+_IMAGE_CODES = base._OBS_CODES  # pylint: disable=protected-access
+_NUMPY_TYPED = (np.dtype(np.uint8), np.dtype(np.float16))   # numpy inputs whose dtype the kernel reads as is
+
+
+def _image_dtype(dtype) -> torch.dtype:
+  """A torch dtype (or its name / numpy dtype) of the four image element types; TypeError otherwise."""
+  if isinstance(dtype, str):
+    dtype = base._OBS_NAMES.get(dtype, dtype)  # pylint: disable=protected-access
+  elif not isinstance(dtype, torch.dtype):
+    try:
+      dtype = torch.from_numpy(np.zeros(0, np.dtype(dtype))).dtype
+    except TypeError:
+      pass
+  if dtype not in _IMAGE_CODES:
+    raise TypeError(f'to_image: image dtype must be float32, uint8, float16 or bfloat16, got {dtype!r}')
+  return dtype
+
+
+def _check_image_dtypes(in_dtype: torch.dtype, out_dtype: torch.dtype):
+  if out_dtype == torch.uint8 and in_dtype != torch.uint8:
+    raise ValueError(f'to_image: uint8 images come from uint8 observations only (got {in_dtype}); '
+                     'a float observation has no defined quantisation')
+
+
+def to_image(shape: Sequence[int], observation, out: Optional[torch.Tensor] = None, batched=None, dtype=None):
   """Converts bsuite observations into an image-like format on the device (wrappers.py:222-247).
 
-  observation: a device tensor `[B, *obs_shape]` (batched; returns a device tensor `[B, *shape]`)
-  or a single numpy observation (returns numpy, like the reference; one H2D + D2H — compatibility
-  path).  Values are tiled (size <= 4) or bilinearly interpolated (skimage >= 0.19 `resize` =
+  observation: a device tensor `[B, *obs_shape]` of float32, uint8, float16 or bfloat16 (batched; returns a device
+  tensor `[B, *shape]`) or a single numpy observation (returns numpy, like the reference; one H2D + D2H —
+  compatibility path).  Values are tiled (size <= 4) or bilinearly interpolated (skimage >= 0.19 `resize` =
   scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True), after skimage's anti-aliasing Gaussian
-  along every axis that shrinks) and broadcast over trailing dims."""
+  along every axis that shrinks) and broadcast over trailing dims.
+
+  dtype: the image's element type, default the observation's (the reference's rule).  Float images (float32, float16,
+  bfloat16) are the float32 image of the observation widened to float32, rounded to nearest-even like `.to(dtype)`.
+  uint8 images come from uint8 observations only (ValueError otherwise) and follow the reference's integer path:
+  float64 filter and interpolation, clipped to the lane's [min, max], truncated.  Numpy uint8 and float16
+  observations go through that typed kernel and return the reference's bits; other numpy dtypes are converted to
+  float32, and the float32 image is cast back to their dtype (or converted to `dtype`)."""
   shape = tuple(int(s) for s in shape)
   if batched is None:
     batched = torch.is_tensor(observation)
   if not batched:
-    obs_np = np.ascontiguousarray(np.asarray(observation, dtype=np.float32))
+    arr = np.asarray(observation)
+    typed = arr.dtype in _NUMPY_TYPED
+    obs_np = np.ascontiguousarray(arr if typed else arr.astype(np.float32))
+    if dtype is not None:
+      dtype = _image_dtype(dtype)
+      if dtype == torch.bfloat16:
+        raise ValueError('to_image: numpy has no bfloat16; pass a device tensor for bfloat16 images')
+      _check_image_dtypes(torch.from_numpy(np.empty(0, obs_np.dtype)).dtype, dtype)
     dev = torch.device('cuda', torch.cuda.current_device())
-    res = to_image(shape, torch.from_numpy(obs_np).to(dev).unsqueeze(0), batched=True)
-    return res[0].cpu().numpy().astype(np.asarray(observation).dtype, copy=False)
+    res = to_image(shape, torch.from_numpy(obs_np).to(dev).unsqueeze(0), batched=True, dtype=dtype)[0].cpu().numpy()
+    return res if typed or dtype is not None else res.astype(arr.dtype, copy=False)
+  # every rule is checked before the first device operation
   obs = observation
-  if obs.dtype != torch.float32 or not obs.is_cuda:
-    raise TypeError('to_image: batched observations must be float32 device tensors')
-  obs = obs.contiguous()
+  if obs.dtype not in _IMAGE_CODES:
+    raise TypeError('to_image: batched observations must be float32, uint8, float16 or bfloat16 device tensors')
+  out_dtype = obs.dtype if dtype is None else _image_dtype(dtype)
+  _check_image_dtypes(obs.dtype, out_dtype)
   B = int(obs.shape[0])
   cfg = _image_cfg(shape, obs.shape[1:])
+  if out is not None and (out.shape != (B,) + shape or out.dtype != out_dtype or not out.is_contiguous()
+                          or out.device != obs.device):
+    raise ValueError(f'to_image: `out` must be a contiguous {out_dtype} tensor of shape (B, *shape) on the same device')
+  if not obs.is_cuda:
+    raise TypeError('to_image: batched observations must be device tensors')
+  obs = obs.contiguous()
   if out is None:
-    out = torch.empty((B,) + shape, dtype=torch.float32, device=obs.device)
-  elif out.shape != (B,) + shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != obs.device:
-    raise ValueError('to_image: `out` must be a contiguous float32 tensor of shape (B, *shape) on the same device')
-  rc = _native.lib.bsx_image_observation(ctypes.byref(cfg), B, obs.data_ptr(), out.data_ptr(),
-                                         torch.cuda.current_stream(obs.device).cuda_stream)
+    out = torch.empty((B,) + shape, dtype=out_dtype, device=obs.device)
+  rc = _native.lib.bsx_image_observation_typed(ctypes.byref(cfg), B, obs.data_ptr(), _IMAGE_CODES[obs.dtype],
+                                               out.data_ptr(), _IMAGE_CODES[out_dtype],
+                                               torch.cuda.current_stream(obs.device).cuda_stream)
   _native.check(rc, 'to_image')
   return out
 
@@ -370,12 +417,24 @@ class ImageObservation(dm_env.EnvironmentBase):
   """Environment wrapper to convert observations to an image-like format (wrappers.py:150-175).
 
   Batched environments keep `num_buffers` image buffers `[B, *shape]` on the device and fill one per
-  call with a single kernel launch; the scalar view returns numpy images like the reference."""
+  call with a single kernel launch; the scalar view returns numpy images like the reference.
 
-  def __init__(self, env, shape: Sequence[int], num_buffers: int = 2):
-    if getattr(env, 'observation_dtype', torch.float32) != torch.float32:
-      raise TypeError(f'ImageObservation converts float32 observations; this environment writes {env.observation_dtype} '
-                      '(construct it with observation_dtype=torch.float32)')
+  dtype: the images' element type.  None keeps the environment's float32 (a narrow environment then needs an explicit
+  `dtype`); otherwise the environment may write any observation dtype and the images are `dtype` (`to_image`'s rules:
+  uint8 images from uint8 observations only).  The scalar view takes float32 and float16."""
+
+  def __init__(self, env, shape: Sequence[int], num_buffers: int = 2, dtype=None):
+    env_dtype = getattr(env, 'observation_dtype', torch.float32)
+    if dtype is None:
+      if env_dtype != torch.float32:
+        raise TypeError(f'ImageObservation converts float32 observations by default; this environment writes '
+                        f'{env_dtype}: pass dtype= (e.g. ImageObservation(env, shape, dtype={env_dtype}))')
+      self._dtype = None
+    else:
+      self._dtype = _image_dtype(dtype)
+      _check_image_dtypes(env_dtype, self._dtype)
+      if getattr(env, '_scalar', False) and self._dtype not in (torch.float32, torch.float16):
+        raise ValueError(f'ImageObservation: the scalar view returns numpy images, float32 or float16 (got {self._dtype})')
     self._env = env
     self._shape = tuple(int(s) for s in shape)
     _image_cfg(self._shape, env.observation_spec().shape)       # validate once, like the first to_image call would
@@ -385,7 +444,8 @@ class ImageObservation(dm_env.EnvironmentBase):
 
   def observation_spec(self):
     spec = self._env.observation_spec()
-    return dm_env.specs.Array(shape=self._shape, dtype=spec.dtype, name=spec.name)
+    dt = spec.dtype if self._dtype is None else base._OBS_SPEC_DTYPES[self._dtype]  # pylint: disable=protected-access
+    return dm_env.specs.Array(shape=self._shape, dtype=dt, name=spec.name)
 
   def action_spec(self):
     return self._env.action_spec()
@@ -393,13 +453,14 @@ class ImageObservation(dm_env.EnvironmentBase):
   def _convert(self, timestep):
     obs = timestep.observation
     if not torch.is_tensor(obs):
-      return timestep._replace(observation=to_image(self._shape, obs))
+      return timestep._replace(observation=to_image(self._shape, obs, dtype=self._dtype))
     if self._images is None:
-      self._images = [torch.empty((obs.shape[0],) + self._shape, dtype=torch.float32, device=obs.device)
+      dt = torch.float32 if self._dtype is None else self._dtype
+      self._images = [torch.empty((obs.shape[0],) + self._shape, dtype=dt, device=obs.device)
                       for _ in range(self._num_buffers)]
     out = self._images[self._buf]
     self._buf = (self._buf + 1) % self._num_buffers
-    return timestep._replace(observation=to_image(self._shape, obs, out=out))
+    return timestep._replace(observation=to_image(self._shape, obs, out=out, dtype=out.dtype))
 
   def reset(self):
     return self._convert(self._env.reset())

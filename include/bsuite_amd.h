@@ -507,6 +507,15 @@ typedef struct {
 } bsx_image_t;
 int bsx_image_observation(const bsx_image_t* cfg, int64_t n_lanes, const float* obs, float* image,
                           void* hip_stream);
+/* Typed images: obs and image in any element code of the observation numbering (0 float32, 1 uint8, 2 float16,
+ * 3 bfloat16 = BSX_CALL_OBS_* >> BSX_CALL_OBS_SHIFT).  Float outputs: the input widened to f32 (exact), the image of
+ * bsx_image_observation, rounded to nearest-even in the output type (torch's `.to(dtype)`).  uint8 output takes uint8
+ * input only and follows the reference's integer path: skimage widens the board to f64, filters and interpolates with
+ * no rounding, clips to the lane's [min, max] and numpy's assignment truncates toward zero.  bsx_image_observation is
+ * the (0, 0) case.  An unknown code is BSX_EINVAL and uint8 output from another input BSX_EMODE, both before any
+ * other check; obs must be aligned to its element size and image to 16 bytes (BSX_EALIGN). */
+int bsx_image_observation_typed(const bsx_image_t* cfg, int64_t n_lanes, const void* obs, int32_t obs_code,
+                                void* image, int32_t image_code, void* hip_stream);
 
 /* ---- misc ---------------------------------------------------------------------------------- */
 int bsx_abi_version(void);
