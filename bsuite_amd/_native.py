@@ -161,6 +161,7 @@ _P = ctypes.c_void_p
 _SIGS = {
     'bsx_abi_version': ([], ctypes.c_int),
     'bsx_observation_dtypes': ([ctypes.c_int32], ctypes.c_int),
+    'bsx_observation_index_width': ([ctypes.c_int32], ctypes.c_int),
     'bsx_row_scratch_bytes': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64], ctypes.c_int64),
     'bsx_bsuite_info': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P],
                         ctypes.c_int),
@@ -229,6 +230,7 @@ CALL_STATE_TAGGED = 1   # BSX_CALL_STATE_TAGGED
 CALL_OBS_SHIFT = 1
 CALL_OBS_MASK = 3 << CALL_OBS_SHIFT
 CALL_OBS_F32, CALL_OBS_U8, CALL_OBS_F16, CALL_OBS_BF16 = (k << CALL_OBS_SHIFT for k in range(4))
+CALL_OBS_INDEX = 1 << 3   # BSX_CALL_OBS_INDEX: out.observation is int32 [B, K] hot-cell numbers (deep_sea K = 1, catch K = 2)
 if lib.bsx_abi_version() != ABI_VERSION:
   raise NativeLibraryError('ABI version mismatch between bsuite_amd/_native.py and libbsuite_amd.so')
 

@@ -52,6 +52,14 @@ __device__ __forceinline__ void bsx_st(P* p, V v) {
   *p = (P)v;
 #endif
 }
+// The policy of one kind of output, in a fused rollout and in an eager step (small_obs.h has the measurements and the rule:
+// a rollout's outputs have no reader inside the call, an eager step's are read by the agent next).
+struct bsx_out_policy { int rollout, eager; };
+constexpr int bsx_policy(bsx_out_policy p, bool rollout) { return rollout ? p.rollout : p.eager; }
+constexpr bsx_out_policy BSX_OUT_SCALARS = {BSX_ST_NT, BSX_ST_WT};        // reward / discount / step_type columns (a wave's store is
+                                                                          // one contiguous 256- / 64-byte range)
+constexpr bsx_out_policy BSX_OUT_INDEX = {BSX_ST_NT, BSX_ST_WT};          // index observation rows (BSX_CALL_OBS_INDEX): one 4- or
+                                                                          // 8-byte store per lane, a wave's 256 / 512 bytes contiguous
 // Per-call values every kernel needs, flattened out of bsx_call_t on the host.
 struct bsx_ctl {
   int64_t n_lanes;
@@ -446,6 +454,121 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_advance_group_kernel(const type
   __shared__ unsigned int s_cnt[2];
   const bsx_group_slot w = bsx_group_find(gi, (int)blockIdx.x);
   bsx_advance_body<Fam>(table[w.seg], w.block, s_fam, s_cnt);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Index observations (bsx_call_t.flags & BSX_CALL_OBS_INDEX): the observation of a lane is the K = HotFn::INDEX_K hot-cell
+// numbers its decoder (deep_sea_hot, catch_hot) reads from the packed state word — int32 rows [B, K] — instead of the
+// board.  25-29 bytes per lane-step and no store stream: a step is a lane advance whose thread also stores the K numbers
+// decoded from the word it has just computed.
+typedef int32_t bsx_i2 __attribute__((ext_vector_type(2)));
+
+// Row `oi` of the index array from the packed state `st`: one store of K * 4 bytes.
+template <int POLICY, class HotFn>
+__device__ __forceinline__ void bsx_index_store(int32_t* __restrict__ rows, int64_t oi, int32_t st, const HotFn& fn) {
+  static_assert(HotFn::INDEX_K == 1 || HotFn::INDEX_K == 2, "index rows are one or two cells");
+  int ha, hb;
+  fn(st, ha, hb);
+  if constexpr (HotFn::INDEX_K == 1) {
+    bsx_st<POLICY>(rows + oi, (int32_t)ha);
+  } else {
+    const bsx_i2 v = {ha, hb};
+    bsx_st<POLICY>(reinterpret_cast<bsx_i2*>(rows) + oi, v);
+  }
+}
+
+// The lean step() / reset() in index mode: ONE launch — bsx_advance_body<Fam, true>'s lane advance, one lane per thread,
+// and the thread stores its lane's index row.  Outputs are an eager step's (write-through: the agent reads them next).
+template <class Fam, class HotFn>
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_index_step_kernel(const typename Fam::args a, int32_t* __restrict__ rows,
+                                                                   const HotFn fn) {
+  __shared__ typename Fam::shared s_fam;
+  __shared__ unsigned int s_cnt[2];
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  Fam::stage(a, s_fam);
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  int type = -1;
+  if (i < a.ctl.n_lanes) {
+    const uint64_t lane = a.ctl.lane_offset + (uint64_t)i;
+    const uint64_t step = bsx_step_of(a.ctl);
+    int32_t nst; double reward;
+    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, i, step);
+    type = Fam::template advance<true>(a, s_fam, i, lane, step, a.state[i], act, nst, reward);
+    a.state[i] = nst;
+    bsx_emit_at<0, 0, false, -1, BSX_OUT_SCALARS.eager>(a.ctl, a.out, i, i, lane, step, type, reward);
+    bsx_index_store<BSX_OUT_INDEX.eager>(rows, i, nst, fn);
+  }
+  bsx_count_types(a.ctl, type, s_cnt);
+  bsx_final_barrier();
+  bsx_flush_counts(a.ctl, s_cnt, blockIdx.x);
+}
+
+// The lean rollout(T) in index mode: ONE launch for all T steps.  The state word stays in a register from its load to
+// its store, the family's tables are staged in LDS once, and the actions are loaded RUN steps ahead of their use: on gfx9
+// loads and stores share one in-order vmcnt, so waiting for a load issued among the stores drains the stores too — one
+// such wait per run instead of one per step (the loop shape of small_obs_regs_rollout, small_obs.h).  LAST / FIRST steps
+// are counted per thread and pooled once per launch.  Outputs [T,B] / [T,B,K] have no reader inside the call: non-temporal.
+template <class Fam, class HotFn>
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_index_rollout_kernel(const typename Fam::args a, const int n_steps,
+                                                                      int32_t* __restrict__ rows, const HotFn fn) {
+  constexpr int RUN = 8;
+  __shared__ typename Fam::shared s_fam;
+  __shared__ unsigned int s_cnt[2];
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  Fam::stage(a, s_fam);
+  __syncthreads();
+  const int64_t B = a.ctl.n_lanes;
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  const bool mine = i < B;
+  const uint64_t lane = a.ctl.lane_offset + (uint64_t)i;
+  const uint64_t step0 = bsx_step_of(a.ctl);
+  int32_t st = mine ? a.state[i] : 0;
+  uint32_t n_last = 0, n_first = 0;
+  // (the workgroup's number waits for the final flush in a VECTOR register: deep_sea's step loop — Philox and the f64 normal
+  // transform of the stochastic variant — leaves no scalar pair free for it, and the compiler would spill one)
+  uint32_t block_id = blockIdx.x;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(block_id));
+#endif
+#pragma unroll 1
+  for (int t0 = 0; t0 < n_steps; t0 += RUN) {
+    const int run = n_steps - t0 < RUN ? n_steps - t0 : RUN;             // uniform
+    int acts[RUN];
+    // (rows beyond the run re-read its last row: no per-row condition mask in scalar registers;
+    // and the threads beyond the batch re-read lane 0: no branch around the loads)
+    const int32_t* const ap = a.action + (int64_t)t0 * B + (mine ? i : 0);
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) acts[j] = ap[(int64_t)(j < run ? j : run - 1) * B];
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_s_waitcnt(0x0070);     // vmcnt(0) lgkmcnt(0): the run's actions have landed, nothing pends inside the run
+#endif
+    // (a rolled loop, the run's action picked by selects: unrolled, the scheduler interleaves the steps' Philox blocks)
+#pragma unroll 1
+    for (int j = 0; j < run; ++j) {
+      int act = acts[0];
+#pragma unroll
+      for (int q = 1; q < RUN; ++q) act = j == q ? acts[q] : act;
+      if (mine) {
+        const int t = t0 + j;
+        const int64_t oi = (int64_t)t * B + i;
+        int32_t nst; double reward;
+        const int type = Fam::template advance<true>(a, s_fam, i, lane, step0 + (uint64_t)t, st, act, nst, reward);
+        st = nst;
+        bsx_emit_at<0, 0, false, -1, BSX_OUT_SCALARS.rollout>(a.ctl, a.out, i, oi, lane, step0 + (uint64_t)t, type, reward);
+        bsx_index_store<BSX_OUT_INDEX.rollout>(rows, oi, nst, fn);
+        n_last += type == BSX_LAST ? 1u : 0u;
+        n_first += type == BSX_FIRST ? 1u : 0u;
+      }
+    }
+  }
+  if (mine) a.state[i] = st;
+  if (a.ctl.counters != nullptr) {
+    if (n_last) atomicAdd(&s_cnt[0], n_last);
+    if (n_first) atomicAdd(&s_cnt[1], n_first);
+  }
+  bsx_final_barrier();
+  bsx_flush_counts(a.ctl, s_cnt, block_id & (BSX_COUNTER_SHARDS - 1));    // (the shard is all bsx_flush_counts takes from it)
 }
 
 // n / cells for n < 2^20 via the host-built magic (bsx_div_magic); cells == 1 has no 32-bit magic.

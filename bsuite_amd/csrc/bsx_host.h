@@ -12,12 +12,17 @@
 // Observation element code of a call (bsx_call_t.flags, BSX_CALL_OBS_*): 0 float32, 1 uint8, 2 float16, 3 bfloat16.
 static inline int bsx_call_obs(const bsx_call_t* call) { return (call->flags & BSX_CALL_OBS_MASK) >> BSX_CALL_OBS_SHIFT; }
 
-// delta_ok / narrow_ok: the family has the delta observation mode (obs_paint) / the narrow observation codes.
+// Index observations (BSX_CALL_OBS_INDEX): out.observation is int32 [n_lanes, K] hot-cell numbers instead of a board.
+static inline bool bsx_call_index(const bsx_call_t* call) { return (call->flags & BSX_CALL_OBS_INDEX) != 0; }
+
+// delta_ok / narrow_ok: the family has the delta observation mode (obs_paint) / the narrow observation codes and the
+// index observations (deep_sea and catch have all of them, nobody else any).
 static inline int bsx_check_call(const bsx_call_t* call, const void* action, const bsx_timestep_t& out,
                                  bool delta_ok = false, bool narrow_ok = false) {
   if (call == nullptr) return BSX_ENULL;
   if (call->obs_paint != nullptr && (!delta_ok || call->n_steps > 1)) return BSX_EMODE;
   if (bsx_call_obs(call) != 0 && (!narrow_ok || call->obs_paint != nullptr)) return BSX_EMODE;
+  if (bsx_call_index(call) && (!narrow_ok || call->obs_paint != nullptr || bsx_call_obs(call) != 0)) return BSX_EMODE;
   if (call->n_lanes < 0 || call->n_lanes > ((int64_t)1 << 40)) return BSX_EINVAL;
   if (call->n_lanes == 0) return 0;
   if (out.reward == nullptr || out.discount == nullptr || out.step_type == nullptr ||
@@ -263,6 +268,7 @@ static int bsx_group_launch_pair(bsx_group* g, int phase, hipStream_t st) {
 static inline int bsx_group_check_set(bsx_group* g, int32_t family, int32_t index, const bsx_call_t* call,
                                       size_t arg_size, size_t arg2_size, int klass) {
   if (g == nullptr || call == nullptr) return BSX_ENULL;
+  if (bsx_call_index(call)) return BSX_EMODE;                                    // groups write dense boards
   if (g->committed || g->family != family || index < 0 || index >= g->n) return BSX_EINVAL;
   if (call->stream.step_base == nullptr || call->force_reset || call->n_steps > 1 || call->n_lanes < 1)
     return BSX_EINVAL;                 // static arguments need a device-resident call counter
@@ -279,6 +285,11 @@ static inline int bsx_group_check_set(bsx_group* g, int32_t family, int32_t inde
 }
 
 static inline int bsx_launch_status() { return (int)hipGetLastError(); }
+
+// Launches bsx_index_decode_kernel (misc.hip): packed state column -> index rows [n_lanes, K] of `family` (BSX_FAM_DEEP_SEA:
+// p0 = N; BSX_FAM_CATCH: p0 = rows, p1 = columns).  `rollout`: the rows are a slice of a rollout's [T,B,K] output.
+int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes, int32_t family, int32_t p0, int32_t p1,
+                            bool rollout, hipStream_t st);
 
 // One call of a two-kernel family (deep_sea, catch): step() / reset() / a rollout of T steps with outputs
 // [T,B,...].  `a` comes from the family's make(); K = stores per thread of its observation stream.
@@ -305,6 +316,29 @@ static int bsx_pair_call(const typename Fam::args& a0, const bsx_call_t* call, c
     s.out.observation = out.observation + off * (int64_t)cells;
     return s;
   };
+  // Index observations (BSX_CALL_OBS_INDEX): no board is written, so none of the size rules below applies.  A lean call is
+  // ONE launch — step() / reset(): bsx_index_step_kernel; rollout(T): bsx_index_rollout_kernel for all T steps — and any
+  // other call (Logging, RewardNoise, MT19937-exact draws, reward_f64) is the unchanged lane advance followed by the
+  // decode kernel state column -> index rows, per step.
+  if (bsx_call_index(call)) {
+    constexpr int IK = HotFn::INDEX_K;
+    int32_t* const rows = reinterpret_cast<int32_t*>(out.observation);
+    const int64_t blocks = (B + BSX_BLOCK - 1) / BSX_BLOCK;
+    if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
+    const dim3 grid((unsigned)blocks), block(BSX_BLOCK);
+    if (bsx_ctl_lean(a0.ctl)) {
+      if (T > 1) bsx_index_rollout_kernel<Fam, HotFn><<<grid, block, 0, st>>>(a0, T, rows, fn);
+      else bsx_index_step_kernel<Fam, HotFn><<<grid, block, 0, st>>>(a0, rows, fn);
+      return bsx_launch_status();
+    }
+    int rc = 0;
+    for (int t = 0; t < T && rc == 0; ++t) {
+      typename Fam::args s = at(t);                        // (the advance never touches the observation)
+      rc = bsx_launch_advance<Fam>(s, st);
+      if (rc == 0) rc = bsx_launch_index_decode(rows + (int64_t)t * B * IK, state, B, HotFn::FAMILY, fn.geom0(), fn.geom1(), T > 1, st);
+    }
+    return rc != 0 ? rc : bsx_launch_status();
+  }
   // Narrow observations (BSX_CALL_OBS_*): lane advance + narrow store stream per step, at every batch size.  Taken before
   // every size rule below: the fused tiles, the pipelined rollout and their byte thresholds are float32-only.
   const int obs_code = bsx_call_obs(call);

@@ -40,7 +40,7 @@ extern "C" int bsx_catch_step(const bsx_catch_t* cfg, const bsx_call_t* call, co
 extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catch_t* cfg, const bsx_call_t* call,
                                    const int32_t* action, int32_t* state, bsx_timestep_t out, double* info) {
   if (g == nullptr) return BSX_ENULL;
-  if (call != nullptr && bsx_call_obs(call) != 0) return BSX_EMODE;          // groups write float32 boards
+  if (call != nullptr && (bsx_call_obs(call) != 0 || bsx_call_index(call))) return BSX_EMODE;   // groups write float32 boards
   int rc;
   catch_fam::args a;
   if (bsx_is_mixed_pair_group(g)) {            // one segment of the mixed two-kernel group

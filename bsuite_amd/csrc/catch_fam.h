@@ -85,6 +85,10 @@ struct catch_fam {
 
 struct catch_hot {
   int rows, cols;
+  static constexpr int INDEX_K = 2;   // int32 values of a lane's index observation: ball, paddle (BSX_CALL_OBS_INDEX)
+  static constexpr int FAMILY = BSX_FAM_CATCH;
+  int geom0() const { return rows; }  // host: what bsx_launch_index_decode rebuilds the decoder from
+  int geom1() const { return cols; }
   __device__ __forceinline__ void operator()(int32_t st, int& a, int& b) const {
     a = ((st >> 8) & 0xFF) * cols + (st & 0xFF);          // ball   (catch.py:111)
     b = (rows - 1) * cols + ((st >> 16) & 0xFF);          // paddle (catch.py:112)

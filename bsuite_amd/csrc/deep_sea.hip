@@ -177,7 +177,7 @@ extern "C" int bsx_deep_sea_step(const bsx_deep_sea_t* cfg, const bsx_call_t* ca
   // two-launch path, whose lane advance goes through bsx_action().)
   static const int step1_env = bsx_env_int("BSX_DEEP_SEA_STEP1", 1);
   if (step1_env != 0 && (int64_t)call->n_lanes * cells * 4 <= ((int64_t)1 << 30) && (call->flags & BSX_CALL_STATE_TAGGED) && call->n_steps <= 1 && call->action_ring <= 1 && cfg->deterministic && bsx_ctl_lean(a.ctl) &&
-      call->obs_paint == nullptr && bsx_call_obs(call) == 0 && (cells & 3u) == 0 && cells >= 3u * 256u) {
+      call->obs_paint == nullptr && bsx_call_obs(call) == 0 && !bsx_call_index(call) && (cells & 3u) == 0 && cells >= 3u * 256u) {
     constexpr int K = 4;
     const uint64_t total = (uint64_t)call->n_lanes * cells;
     const uint64_t blocks = (total + (uint64_t)K * 4 * BSX_BLOCK - 1) / ((uint64_t)K * 4 * BSX_BLOCK);
@@ -193,7 +193,7 @@ extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_d
                                       const bsx_call_t* call, const int32_t* action, int32_t* state,
                                       bsx_timestep_t out, double* info) {
   if (g == nullptr) return BSX_ENULL;
-  if (call != nullptr && bsx_call_obs(call) != 0) return BSX_EMODE;          // groups write float32 boards
+  if (call != nullptr && (bsx_call_obs(call) != 0 || bsx_call_index(call))) return BSX_EMODE;   // groups write float32 boards
   int rc;
   deep_sea_fam::args a;
   if (bsx_is_mixed_pair_group(g)) {            // one segment of the mixed two-kernel group

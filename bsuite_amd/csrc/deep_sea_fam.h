@@ -103,6 +103,10 @@ struct deep_sea_fam {
 // hot cell of a lane from its packed state (observation stream kernel)
 struct deep_sea_hot {
   int N;
+  static constexpr int INDEX_K = 1;   // int32 values of a lane's index observation (BSX_CALL_OBS_INDEX)
+  static constexpr int FAMILY = BSX_FAM_DEEP_SEA;
+  int geom0() const { return N; }     // host: what bsx_launch_index_decode rebuilds the decoder from
+  int geom1() const { return 0; }
   __device__ __forceinline__ void operator()(int32_t st, int& a, int& b) const {
     const int row = st & 0xFF, col = (st >> 8) & 0xFF;
     a = row < N ? row * N + col : -1;     // deep_sea.py:105-107 (terminal observation is all-zero)

@@ -12,6 +12,38 @@ extern "C" int bsx_observation_dtypes(int32_t family) {
   return (family >= 0 && family <= BSX_FAM_SWEEP_MIXED) ? 0x1 : 0;
 }
 
+extern "C" int bsx_observation_index_width(int32_t family) {
+  return family == BSX_FAM_DEEP_SEA ? deep_sea_hot::INDEX_K : family == BSX_FAM_CATCH ? catch_hot::INDEX_K : 0;
+}
+
+// Index observations of a call that is not lean (BSX_CALL_OBS_INDEX under Logging / RewardNoise / MT19937-exact draws /
+// reward_f64): the unchanged lane advance has written the packed state column, this decodes it into the index rows —
+// one lane per thread, a wave writes one contiguous 256-byte (deep_sea) or 512-byte (catch) range.  The family is a
+// uniform switch; p0 / p1 are the decoder's geometry (deep_sea: N; catch: rows, columns).  `rollout`: slice t of a
+// [T,B,K] array (BSX_OUT_INDEX.rollout), else an eager step's rows (BSX_OUT_INDEX.eager).
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_index_decode_kernel(int32_t* __restrict__ rows, const int32_t* __restrict__ state,
+                                                                     int64_t n_lanes, int32_t family, int32_t p0, int32_t p1,
+                                                                     int32_t rollout) {
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  if (i >= n_lanes) return;
+  const int32_t st = state[i];
+  if (family == BSX_FAM_DEEP_SEA) {
+    if (rollout) bsx_index_store<BSX_OUT_INDEX.rollout>(rows, i, st, deep_sea_hot{p0});
+    else bsx_index_store<BSX_OUT_INDEX.eager>(rows, i, st, deep_sea_hot{p0});
+  } else {
+    if (rollout) bsx_index_store<BSX_OUT_INDEX.rollout>(rows, i, st, catch_hot{p0, p1});
+    else bsx_index_store<BSX_OUT_INDEX.eager>(rows, i, st, catch_hot{p0, p1});
+  }
+}
+
+int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes, int32_t family, int32_t p0, int32_t p1,
+                            bool rollout, hipStream_t st) {
+  const int64_t blocks = (n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
+  bsx_index_decode_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(rows, state, n_lanes, family, p0, p1, rollout ? 1 : 0);
+  return 0;
+}
+
 extern "C" const char* bsx_strerror(int code) {
   switch (code) {
     case 0: return "ok";
@@ -19,7 +51,7 @@ extern "C" const char* bsx_strerror(int code) {
     case BSX_ENULL: return "required pointer is NULL";
     case BSX_EALIGN: return "observation buffer (or row scratch) is not 16-byte aligned";
     case BSX_ERANGE: return "parameter outside the supported range of this family";
-    case BSX_EMODE: return "combination not available (randn in MT19937-exact mode; obs_paint with a rollout, a group or a family without a board; a narrow observation type outside a single deep_sea / catch call or with obs_paint)";
+    case BSX_EMODE: return "combination not available (randn in MT19937-exact mode; obs_paint with a rollout, a group or a family without a board; a narrow observation type or index observations outside a single deep_sea / catch call or with obs_paint)";
     case BSX_ENOMEM: return "host allocation failed";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown bsx error";
   }

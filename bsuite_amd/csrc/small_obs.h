@@ -95,16 +95,13 @@ struct bsx_reset_pool {
 // faster everywhere (ab_eager_output_policy.log).  NEITHER for rows written as 8-byte pieces at the row stride (cartpole
 // row-per-lane: 18 -> 25 us non-temporal — partial lines want the L2 to merge them).  deep_sea / catch / mnist / the sweep are
 // not touched by this (ab_small_nt_other_paths.log).  The policy of each kind of output, in a fused rollout and in an eager step:
-struct bsx_out_policy { int rollout, eager; };
-constexpr bsx_out_policy BSX_OUT_SCALARS = {BSX_ST_NT, BSX_ST_WT};        // reward / discount / step_type columns (a wave's store is
-                                                                          // one contiguous 256- / 64-byte range)
+// (struct bsx_out_policy, bsx_policy, BSX_OUT_SCALARS — the reward / discount / step_type columns — and BSX_OUT_INDEX: bsx_device.h)
 constexpr bsx_out_policy BSX_OUT_ROW12 = {BSX_ST_NT, BSX_ST_WT};          // rows of one or two floats stored by their own thread
 constexpr bsx_out_policy BSX_OUT_STAGED = {BSX_ST_NT, BSX_ST_WT};         // rows staged through a wave's LDS, stored as 16-byte chunks
 constexpr bsx_out_policy BSX_OUT_PARTIAL = {BSX_ST_PLAIN, BSX_ST_PLAIN};  // rows of 4 / 6 / 8 floats stored by their own thread as
                                                                           // 8-byte pieces at the row stride (partial lines)
 constexpr bsx_out_policy BSX_OUT_ROW3 = {BSX_ST_NT, BSX_ST_WT};           // rows of three floats (one 12-byte store per lane)
 constexpr bsx_out_policy BSX_OUT_TILE = {BSX_ST_NT, BSX_ST_WT};           // the 16-byte chunks of the wide rows' bit-plane tiles
-constexpr int bsx_policy(bsx_out_policy p, bool rollout) { return rollout ? p.rollout : p.eager; }
 // Per family: does the fused rollout store reward / discount / step_type non-temporal?
 template <class Env> struct small_rollout_nt_scalars { static constexpr bool value = true; };
 

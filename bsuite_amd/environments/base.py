@@ -49,7 +49,8 @@ _current_device = getattr(torch._C, '_cuda_getDevice', None) or torch.cuda.curre
 _OBS_CODES = {torch.float32: 0, torch.uint8: 1, torch.float16: 2, torch.bfloat16: 3}
 _OBS_NAMES = {'float32': torch.float32, 'uint8': torch.uint8, 'float16': torch.float16, 'bfloat16': torch.bfloat16}
 _OBS_SPEC_DTYPES = {torch.float32: np.float32, torch.uint8: np.uint8, torch.float16: np.float16,
-                    torch.bfloat16: np.float32}     # numpy has no bfloat16: see Environment.observation_spec
+                    torch.bfloat16: np.float32,     # numpy has no bfloat16: see Environment.observation_spec
+                    torch.int32: np.int32}          # observation_mode='index' (never an observation_dtype a caller may pass)
 
 
 def _resolve_seed(seed: Optional[int]) -> int:
@@ -68,6 +69,7 @@ class Environment(dm_env.EnvironmentBase):
   # Subclass constants.
   _supports_delta = False  # families whose observation is a board with <= 2 hot cells
   _supports_narrow_obs = False  # families whose observations are all 0/1: observation_dtype may be narrower than float32
+  _index_width = 0  # observation_mode='index': int32 values per lane (bsx_observation_index_width), 0 = the family has no such mode
   _pipelined_rollout = False  # two-kernel families whose rollouts are software-pipelined (state_alt)
   _state_alt = None
   scalar_host_buffers = True   # scalar view: TimeStep / action buffers in pinned host memory mapped into the device (class
@@ -132,11 +134,25 @@ class Environment(dm_env.EnvironmentBase):
     # stores per lane instead of the whole board).  The tensors returned are identical to the dense
     # mode's; the caller must treat them as read-only.  Its throughput is reported separately from
     # the dense contract (bench.py --observation-mode delta).
-    if observation_mode not in ('dense', 'delta'):
-      raise ValueError("observation_mode must be 'dense' or 'delta'")
+    # observation_mode='index' (deep_sea, catch): the observation is the int32 numbers of the board's hot cells, [B, K] —
+    # deep_sea K = 1: row * N + column, -1 on the all-zero terminal board; catch K = 2: the ball's cell, the paddle's cell —
+    # instead of the board: 25-29 bytes per lane-step, a step is ONE lane-advance-sized launch and a rollout one launch for
+    # all T steps.  Everything else a call returns or updates is the dense mode's.  Batched, float32-typed, single
+    # environments only; checked here, before any GPU use.  (utils/observations.py: index_to_dense, index_embedding)
+    if observation_mode not in ('dense', 'delta', 'index'):
+      raise ValueError("observation_mode must be 'dense', 'delta' or 'index'")
     if observation_mode == 'delta' and not self._supports_delta:
       raise ValueError(f'{type(self).__name__} has no delta observation mode (its observations are small and dense)')
     self._delta = observation_mode == 'delta'
+    self._index = observation_mode == 'index'
+    self._board_shape = self._obs_shape
+    if self._index:
+      if not self._index_width:
+        raise ValueError(f'{type(self).__name__} has no index observation mode (its observations are not one-hot boards)')
+      if self._scalar:
+        raise ValueError("observation_mode='index' needs the batched view (batch=B)")
+      if obs_allocator is not None:
+        raise ValueError("observation_mode='index' is not available in SweepBatch (float32 arenas)")
     # observation_dtype (deep_sea, catch): the element type the engine writes its observations in — float32, or uint8 /
     # float16 / bfloat16, which hold the boards' 0.0 and 1.0 exactly in a quarter / half of the bytes.  Batched, dense,
     # single environments only; checked here, before any GPU use.
@@ -152,8 +168,13 @@ class Environment(dm_env.EnvironmentBase):
         raise ValueError("observation_dtype other than float32 needs observation_mode='dense'")
       if obs_allocator is not None:
         raise ValueError('observation_dtype other than float32 is not available in SweepBatch (float32 arenas)')
+    if self._index and dt != torch.float32:
+      raise ValueError("observation_mode='index' writes int32 cell numbers: observation_dtype must stay float32")
     self._obs_dtype = dt
     self._obs_flags = _OBS_CODES[dt] << _native.CALL_OBS_SHIFT
+    if self._index:           # from here on the observation IS the [K] int32 row; board_shape keeps the dense shape
+      self._obs_shape, self._obs_dtype = (self._index_width,), torch.int32
+      self._obs_flags = _native.CALL_OBS_INDEX
     if rng not in ('philox', 'mt19937'):
       raise ValueError("rng must be 'philox' or 'mt19937'")
     self._rng_mode = rng
@@ -193,6 +214,16 @@ class Environment(dm_env.EnvironmentBase):
   def observation_dtype(self) -> torch.dtype:
     """The torch dtype of the observation tensors step() / reset() / rollout() return."""
     return self._obs_dtype
+
+  @property
+  def observation_mode(self) -> str:
+    """'dense', 'delta' or 'index' (read-only: fixed at construction)."""
+    return 'index' if self._index else 'delta' if self._delta else 'dense'
+
+  @property
+  def board_shape(self):
+    """The shape of one lane's dense observation, in every observation mode (deep_sea (N, N), catch (rows, columns))."""
+    return self._board_shape
 
   @property
   def lane_offset(self) -> int:
@@ -252,6 +283,8 @@ class Environment(dm_env.EnvironmentBase):
     (memory_chain / umbrella_chain with wide rows, whole-sweep groups): the segment leaves its rows packed there and the
     group's store stream decodes them.  `state_alt` (two-kernel families, pipelined sweeps): the lane advance reads that
     column and writes the environment's own; with `swap_state` the roles are exchanged."""
+    if self._index:           # (before anything is allocated or launched)
+      raise ValueError("grouped launches write dense observations; use observation_mode='dense'")
     self._ensure_allocated()
     ring = int(action.shape[0]) if (torch.is_tensor(action) and action.dim() == 2) else 0
     if (not torch.is_tensor(action) or action.dtype != torch.int32 or action.device != self._device
@@ -657,7 +690,7 @@ class Environment(dm_env.EnvironmentBase):
     call = self._call_desc
     call.force_reset = 0
     call.n_steps = T
-    if self._pipelined_rollout and T > 1:
+    if self._pipelined_rollout and T > 1 and not self._index:     # (no boards, no store stream to pipeline)
       # deep_sea / catch: a scratch state column lets every launch after the first carry the observation
       # stream of step t beside the lane advance of step t+1 (bsx_call_t.state_alt)
       if self._state_alt is None:
@@ -697,6 +730,9 @@ class Environment(dm_env.EnvironmentBase):
     """Shape and dtype of one lane's observation.  With observation_dtype=torch.bfloat16 the dtype reported is
     np.float32 (numpy has no bfloat16) while the tensors are bfloat16: every value the spec allows (0.0 and 1.0 for
     the boards that support narrow types) is exact in it, and `observation_dtype` is the authority."""
+    if self._index:     # K cell numbers of the dense board, -1 = none (deep_sea's all-zero terminal board)
+      return specs.BoundedArray(shape=self._obs_shape, dtype=np.int32, name='observation', minimum=-1,
+                                maximum=int(np.prod(self._board_shape)) - 1)
     return specs.Array(shape=self._obs_shape, dtype=self._obs_spec_dtype(), name='observation')
 
   def _obs_spec_dtype(self):

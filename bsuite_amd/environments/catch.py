@@ -43,6 +43,7 @@ class Catch(base.Environment):
   _abi_name = 'catch'
   _supports_delta = True
   _supports_narrow_obs = True
+  _index_width = 2
   _pipelined_rollout = True
 
   def _native_args(self, call, action_ptr, out):
@@ -53,6 +54,8 @@ class Catch(base.Environment):
 
   def observation_spec(self) -> specs.BoundedArray:
     """A BoundedArray in [0, 1]; for observation_dtype=torch.bfloat16 its dtype is np.float32 (base.Environment.observation_spec)."""
+    if self._index:
+      return super().observation_spec()
     return specs.BoundedArray(shape=self._obs_shape, dtype=self._obs_spec_dtype(), name='observation',
                               minimum=0, maximum=1)
 

@@ -70,6 +70,7 @@ class DeepSea(base.Environment):
   _abi_name = 'deep_sea'
   _supports_delta = True
   _supports_narrow_obs = True
+  _index_width = 1
   _pipelined_rollout = True
 
   # Bit 18 of the packed state word = the parity of the call index that reads it next (csrc/deep_sea_fam.h: every

@@ -82,6 +82,8 @@ class SweepBatch:
     self.device = torch.device('cuda:0' if device is None else device)
     env_kwargs = env_kwargs or {}
     for name, kw in env_kwargs.items():
+      if kw.get('observation_mode') == 'index':
+        raise ValueError(f"SweepBatch writes dense float32 observations into one arena ({name}: observation_mode='index')")
       if kw.get('observation_dtype', torch.float32) not in (torch.float32, 'float32'):
         raise ValueError(f'SweepBatch writes float32 observations into one arena ({name}: observation_dtype='
                          f'{kw["observation_dtype"]!r})')

@@ -1,0 +1,41 @@
+"""Helpers for index observations (observation_mode='index' of deep_sea and catch).
+
+An index observation names the hot cells of a one-hot board: int32 `[..., K]`, each entry a flat cell number of the
+dense board (`env.board_shape`) or -1 for "no cell" (deep_sea's all-zero terminal board).  Pure torch: they work on
+any device and on any leading dimensions (`[B, K]` from step(), `[T, B, K]` from rollout()).
+"""
+from typing import Optional, Sequence
+
+import torch
+
+
+def index_to_dense(index: torch.Tensor, board_shape: Sequence[int], dtype: torch.dtype = torch.float32,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """The dense boards `[..., *board_shape]` an index observation `[..., K]` stands for: zeros with a one at every entry
+  >= 0 (entries that name the same cell give one 1, as in the dense observation).  `out`, if given, is overwritten."""
+  board_shape = tuple(int(s) for s in board_shape)
+  cells = 1
+  for s in board_shape:
+    cells *= s
+  lead = tuple(index.shape[:-1])
+  if out is None:
+    out = torch.zeros(lead + board_shape, dtype=dtype, device=index.device)
+  else:
+    if tuple(out.shape) != lead + board_shape or not out.is_contiguous() or out.device != index.device:
+      raise ValueError(f'index_to_dense: `out` must be a contiguous tensor of shape {lead + board_shape} on {index.device}')
+    out.zero_()
+  idx = index.reshape(-1, index.shape[-1]).to(torch.int64)
+  flat = out.view(-1, cells)
+  # -1 entries go to a scratch column behind the board, which is dropped: no data-dependent control flow, no host sync
+  padded = torch.zeros((flat.shape[0], cells + 1), dtype=out.dtype, device=out.device)
+  padded.scatter_(1, torch.where(idx >= 0, idx, torch.full_like(idx, cells)), 1)
+  flat.copy_(padded[:, :cells])
+  return out
+
+
+def index_embedding(index: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+  """`sum_k table[index[..., k] + 1]`: the gather form of `board.reshape(..., cells) @ W` for a one-hot board, with
+  `table` = `[cells + 1, D]` whose row 0 is zero (the row -1 selects) and whose row c + 1 is `W[c]`.  For catch the two
+  rows of ball and paddle are summed, also when they name the same cell — there the dense board holds ONE 1, so the
+  two forms differ on the step where the paddle catches the ball; use index_to_dense where that matters."""
+  return table[index.to(torch.int64) + 1].sum(dim=-2)

@@ -424,6 +424,9 @@ class ImageObservation(dm_env.EnvironmentBase):
   uint8 images from uint8 observations only).  The scalar view takes float32 and float16."""
 
   def __init__(self, env, shape: Sequence[int], num_buffers: int = 2, dtype=None):
+    if getattr(env, 'observation_mode', 'dense') == 'index':
+      raise TypeError("ImageObservation converts boards; this environment writes int32 cell numbers (observation_mode="
+                      "'index'): build it with observation_mode='dense'")
     env_dtype = getattr(env, 'observation_dtype', torch.float32)
     if dtype is None:
       if env_dtype != torch.float32:

@@ -2,10 +2,16 @@
 reads the observation tensor the engine just wrote — no host round trip anywhere in the loop.
 
     python examples/closed_loop_policy.py [bsuite_id] [lanes] [steps] [--observation-dtype float32|uint8|float16|bfloat16]
+                                          [--observation-mode dense|index]
 
 With a narrow --observation-dtype (deep_sea, catch) the engine writes the boards as bytes or 16-bit floats, and the policy
 converts each board once, as it reads it: to float32 from uint8, not at all from float16 / bfloat16, whose weights and
 matrix product stay in that type.
+
+With --observation-mode index (deep_sea, catch) the engine writes the numbers of the board's hot cells instead of the
+board, and the same linear policy is a row gather: `board @ W` of a one-hot board is `W[cell]` (summed over the ball's and
+the paddle's cell for catch; a cell they share counts once, as on the board) — the same float32 logits as the dense run
+for the same weights, without the board ever being written or read.
 
 This is the batched counterpart of the reference run loop (bsuite/baselines/experiment.py:43-57):
 `timestep = env.step(agent.select_action(timestep))`, with 2^20 environments per call.
@@ -20,6 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from a checkout
 import bsuite_amd  # noqa: E402
+from bsuite_amd.utils import observations  # noqa: E402
 
 
 def main():
@@ -28,19 +35,31 @@ def main():
   ap.add_argument('lanes', nargs='?', type=int, default=1 << 20)
   ap.add_argument('steps', nargs='?', type=int, default=200)
   ap.add_argument('--observation-dtype', default='float32', choices=('float32', 'uint8', 'float16', 'bfloat16'))
+  ap.add_argument('--observation-mode', default='dense', choices=('dense', 'index'))
   a = ap.parse_args()
   bsuite_id, lanes, steps = a.bsuite_id, a.lanes, a.steps
-  env = bsuite_amd.load_from_id(bsuite_id, batch=lanes, seed=0, observation_dtype=a.observation_dtype)
-  n_obs = int(torch.tensor(env.observation_spec().shape).prod())
+  index = a.observation_mode == 'index'
+  env = bsuite_amd.load_from_id(bsuite_id, batch=lanes, seed=0, observation_dtype=a.observation_dtype,
+                                observation_mode=a.observation_mode)
+  n_obs = int(torch.tensor(env.board_shape if index else env.observation_spec().shape).prod())
   n_act = env.action_spec().num_values
-  compute = env.observation_dtype if env.observation_dtype.is_floating_point else torch.float32
+  compute = torch.float32 if index or not env.observation_dtype.is_floating_point else env.observation_dtype
   g = torch.Generator(device='cuda').manual_seed(0)
   weights = torch.randn((n_obs, n_act), device='cuda', generator=g).to(compute)
+  table = torch.cat([torch.zeros((1, n_act), device='cuda', dtype=compute), weights]) if index else None   # row 0: "no cell"
 
-  def policy(timestep):                           # greedy over a linear read-out of the observation
+  def logits_of(timestep):                        # a linear read-out of the observation
+    if index:
+      cells = timestep.observation                                     # int32 [lanes, K]
+      if cells.shape[1] == 2:                                          # catch: a cell ball and paddle share is ONE 1 on the board
+        cells = torch.where((cells[:, 1:] == cells[:, :1]).expand(-1, 2) & torch.tensor([False, True], device=cells.device),
+                            torch.full_like(cells, -1), cells)
+      return observations.index_embedding(cells, table)
     board = timestep.observation.reshape(lanes, n_obs).to(compute)      # the one conversion (none for a float board)
-    logits = board @ weights
-    return logits.argmax(dim=1).to(torch.int32)
+    return board @ weights
+
+  def policy(timestep):                           # greedy
+    return logits_of(timestep).argmax(dim=1).to(torch.int32)
 
   ts = env.reset()
   for _ in range(20):
@@ -52,7 +71,7 @@ def main():
   torch.cuda.synchronize()
   dt = time.perf_counter() - t0
   info = {k: float(v.sum()) for k, v in env.bsuite_info().items()}
-  print(json.dumps(dict(bsuite_id=bsuite_id, observation_dtype=a.observation_dtype, lanes=lanes, steps=steps, ms_per_step=round(dt / steps * 1e3, 4),
+  print(json.dumps(dict(bsuite_id=bsuite_id, observation_dtype=a.observation_dtype, observation_mode=a.observation_mode, lanes=lanes, steps=steps, ms_per_step=round(dt / steps * 1e3, 4),
                         env_steps_per_s=round(lanes * steps / dt), episodes_finished=int(env.episode_counters()[0]),
                         bsuite_info_sums=info)))
 

@@ -227,6 +227,25 @@ typedef struct {
 #define BSX_CALL_OBS_F16 (2 << BSX_CALL_OBS_SHIFT)   /* IEEE binary16, one = 0x3C00         */
 #define BSX_CALL_OBS_BF16 (3 << BSX_CALL_OBS_SHIFT)  /* bfloat16, one = 0x3F80              */
 
+/* Index observations (a flags bit; 0 = a board, as before): deep_sea and catch observations are boards of zeros with one
+ * or two ones, and with this bit a call writes the numbers of the hot cells instead of the board.  `out.observation`
+ * (still declared float*, still 16-byte aligned) then points to n_lanes * K int32_t, K = bsx_observation_index_width
+ * (family) — [T,B,K] in a rollout, slice t starting t * B * K * 4 bytes in:
+ *   deep_sea  K = 1: row * N + column of the diver, or -1 on the terminal observation (the all-zero board);
+ *   catch     K = 2: the ball's cell ball_y * columns + ball_x, then the paddle's cell (rows - 1) * columns + paddle_x;
+ *             both always written, also when they name the same cell.
+ * Scattering 1.0 at every entry >= 0 of a lane's row into a zero board gives the board the call would have written;
+ * every other output, the state and info columns, the counters and the draw stream are those of the board call.
+ * A call without Logging / RewardNoise / MT19937-exact draws / reward_f64 is ONE launch (a rollout: one for all T
+ * steps); any other call is the usual lane advance followed by a small decode kernel, per step.  BSX_EMODE, before any
+ * device work, for any other family, together with a non-zero element code or obs_paint, and in a group
+ * (bsx_group_set_*). */
+#define BSX_CALL_OBS_INDEX (1 << 3)
+
+/* int32 values per lane of an index observation (BSX_CALL_OBS_INDEX): 1 for deep_sea, 2 for catch, 0 for every family
+ * without the mode and for unknown ids.  Host only. */
+int bsx_observation_index_width(int32_t family);
+
 /* Bit k set: family `family` (BSX_FAM_*) accepts observation code k (flags field BSX_CALL_OBS_*, k = 0..3): 0xF for
  * deep_sea and catch, 0x1 (float32 only) for the other families and groups, 0 for an unknown family.  Host only. */
 int bsx_observation_dtypes(int32_t family);
