@@ -165,6 +165,7 @@ _SIGS = {
     'bsx_row_scratch_bytes': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64], ctypes.c_int64),
     'bsx_bsuite_info': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P],
                         ctypes.c_int),
+    'bsx_lane_reset_mark': ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _P, _P, _P, ctypes.c_int32, _P], ctypes.c_int),
     'bsx_strerror': ([ctypes.c_int], ctypes.c_char_p),
     'bsx_calib_fill': ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     'bsx_calib_copy': ([_P, _P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "bsx_host.h"
+#include "bsx_lane_reset.h"
 #include "pair_mixed.h"
 
 extern "C" int bsx_abi_version(void) { return BSX_ABI_VERSION; }
@@ -158,6 +159,41 @@ extern "C" int bsx_bsuite_info(int32_t family, int32_t variant, int64_t n_lanes,
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   bsuite_info_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
       family, variant, n_lanes, state, info, n_info, pending ? 1 : 0, info_out);
+  return bsx_launch_status();
+}
+
+// Per-lane reset (step(actions, reset_mask=) of the Python classes): marks the lanes whose mask byte is non-zero so that
+// their next call — a step, or the first step of a rollout — takes the path of an explicit reset().  One lane per thread,
+// the family a uniform switch inside bsx_lane_reset_word (bsx_lane_reset.h, which the CPU tests run through gcc): one
+// coalesced byte load per lane; a masked lane whose reset bit is not set yet reads its state word, ORs the bit in and —
+// classic cartpole / mountain_car with per-episode info columns — folds the abandoned episode's return into column 0,
+// as the forced branch of its step does.  Unmasked lanes, and lanes that reset anyway, are not written.  Plain stores: the
+// next launch on the stream reads the column from L2.  It draws nothing and reads no call index.
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_lane_reset_kernel(const uint8_t* __restrict__ mask, int32_t* __restrict__ state,
+                                                                   double* __restrict__ info, int64_t n_lanes, int32_t family,
+                                                                   int32_t variant, int32_t folded) {
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  if (i >= n_lanes) return;
+  if (mask[i] == 0) return;
+  const int32_t st = state[i];
+  double delta;
+  const int32_t nst = bsx_lane_reset_word(st, family, variant, folded, &delta);
+  if (nst == st) return;
+  state[i] = nst;
+  if (delta != 0.0) info[i] += delta;                 // (only where bsx_lane_reset_folds: info was checked by the host)
+}
+
+extern "C" int bsx_lane_reset_mark(int32_t family, int32_t variant, int64_t n_lanes, const uint8_t* mask, int32_t* state,
+                                   double* info, int32_t folded, void* hip_stream) {
+  if (family < BSX_FAM_DEEP_SEA || family > BSX_FAM_MNIST || n_lanes < 0) return BSX_EINVAL;
+  if (n_lanes == 0) return 0;
+  if (mask == nullptr || state == nullptr) return BSX_ENULL;
+  const int folds = bsx_lane_reset_folds(family, variant, folded);
+  if (folds && info == nullptr) return BSX_ENULL;
+  const int64_t blocks = (n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
+  bsx_lane_reset_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
+      mask, state, info, n_lanes, family, variant, folds);
   return bsx_launch_status();
 }
 

@@ -962,9 +962,12 @@ static int launch_small_obs(const typename Env::args& a, int n_steps, void* hip_
         const uint64_t sblocks = bsx_flat_blocks((uint64_t)a.ctl.n_lanes * sg.numel, k);
         if (sblocks > 0x7FFFFFFFull) return BSX_EINVAL;
         const dim3 gs((unsigned)sblocks);
+#ifdef BSX_TUNING     // (the knob is read in the tuning build only: the product library carries the K = 2 stream alone)
         if (k == 1) bsx_row_stream_kernel<typename Env::rows_t, 1><<<gs, b, 0, st>>>(sg);
         else if (k == 4) bsx_row_stream_kernel<typename Env::rows_t, 4><<<gs, b, 0, st>>>(sg);
-        else bsx_row_stream_kernel<typename Env::rows_t, 2><<<gs, b, 0, st>>>(sg);
+        else
+#endif
+        bsx_row_stream_kernel<typename Env::rows_t, 2><<<gs, b, 0, st>>>(sg);
         return bsx_launch_status();
       }
       SMALL_OBS_LAUNCH(false)

@@ -454,6 +454,9 @@ class Environment(dm_env.EnvironmentBase):
     # (state / info pointers never move: load_state_dict copies in place), the nested structs of the call
     # descriptor, and the TimeStep tuples the batched view returns.
     self._fn = getattr(_native.lib, f'bsx_{self._abi_name}_step')
+    # per-lane reset marks (bsx_lane_reset_mark): the family, and the column that carries its reset_next bit
+    self._family_id = _native.FAMILY_IDS[self._abi_name]
+    self._reset_column = 'steps' if 'steps' in self._state else 'state'
     self._argv = [list(self._native_args(self._call_desc, 0, p)) for p in self._out_ptrs]
     self._call_stream, self._call_wrap = self._call_desc.stream, self._call_desc.wrap     # views of the same memory
     self._wrap_applied = None
@@ -638,18 +641,67 @@ class Environment(dm_env.EnvironmentBase):
       self._ensure_allocated()
     return self._wrap_output(self._call(0, force_reset=True))
 
-  def step(self, action) -> dm_env.TimeStep:
+  def step(self, action, reset_mask=None) -> dm_env.TimeStep:
     """Steps every lane; lanes whose previous step was LAST (or that are fresh) reset instead and
-    ignore their action (base.py:59-65)."""
+    ignore their action (base.py:59-65).
+
+    reset_mask (batched view): a bool or uint8 device tensor [B].  Lane i with reset_mask[i] != 0 does what the
+    reference instance does on reset() — a FIRST TimeStep, its action ignored, the running episode abandoned — while
+    the other lanes step: B reference instances, each called with reset() or step(a) as its own mask element says.  It is
+    `mark_reset(reset_mask)` followed by `step(action)` on the same stream (one small launch more); None is the plain
+    step, launch for launch."""
     if not self._allocated:
+      if reset_mask is not None:
+        self._check_reset_mask(reset_mask)
       self._ensure_allocated()
-    if (type(action) is torch.Tensor and action.dtype is torch.int32 and action.is_cuda and action.dim() == 1
+    if reset_mask is None and (
+        type(action) is torch.Tensor and action.dtype is torch.int32 and action.is_cuda and action.dim() == 1
         and action.size(0) == self._batch and action.is_contiguous() and action.get_device() == self._dev_index
         and not self._scalar):
       ptr = action.data_ptr()                  # the common call: nothing to convert
     else:
+      if reset_mask is not None:
+        self._check_reset_mask(reset_mask)     # (every refusal before the action is looked at or anything is launched)
       ptr = self._coerce_actions(action).data_ptr()
+      if reset_mask is not None:
+        self._mark_reset(reset_mask)
     return self._wrap_output(self._call(ptr, force_reset=False))
+
+  def _check_reset_mask(self, mask):
+    """The refusals of mark_reset() / step(reset_mask=): all of them before any GPU use."""
+    if self._scalar:
+      raise ValueError('reset_mask / mark_reset() need the batched view (batch=B); reset() is the one lane of the '
+                       'scalar view')
+    if getattr(self, '_grouped_by', None) is not None:
+      # (a pipelined pair of prepared groups holds a CLONE of the packed state column: a mark in this one would be lost)
+      raise RuntimeError('mark_reset() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
+    if (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self._device
+        or tuple(mask.shape) != (self._batch,) or not mask.is_contiguous()):
+      raise ValueError(f'reset_mask must be a contiguous bool or uint8 tensor of shape ({self._batch},) on '
+                       f'{self._device}')
+
+  def _mark_reset(self, mask):
+    if _current_device() != self._dev_index:
+      with torch.cuda.device(self._device):
+        return self._mark_reset(mask)
+    col = self._info_pending_column
+    # `folded`: the info columns are maintained per episode (no Logging) — where _info_columns() decides it
+    folded = 1 if (self._logging is None and col is not None) else 0
+    rc = _native.lib.bsx_lane_reset_mark(
+        self._family_id, self._info_variant, self._batch, mask.data_ptr(),
+        self._state[self._reset_column].data_ptr(), self._info.data_ptr(), folded, _current_raw_stream(self._dev_index))
+    if rc != 0:
+      _native.check(rc, f'{type(self).__name__} mark_reset')
+    return None
+
+  def mark_reset(self, mask):
+    """Marks the lanes with mask[i] != 0 (bool or uint8 device tensor [B]) for reset without stepping: each takes the
+    path of an explicit reset() at its next call — a step(), or the first step of a rollout().  Marking draws nothing
+    and consumes no call index; a lane that resets anyway (fresh, or after LAST) is left as it is, and marking twice is
+    marking once.  Asynchronous on the current stream, capturable into a HIP graph (the mask is read in place)."""
+    self._check_reset_mask(mask)
+    self._ensure_allocated()
+    self._mark_reset(mask)
 
   def rollout(self, actions) -> dm_env.TimeStep:
     """T consecutive step() calls in one entry-point call (batched view only).

@@ -53,8 +53,14 @@ class _RewardWrapper(dm_env.EnvironmentBase):
   def reset(self):
     return self._env.reset()
 
-  def step(self, action):
-    return self._env.step(action)
+  def step(self, action, reset_mask=None):
+    if reset_mask is None:
+      return self._env.step(action)
+    return self._env.step(action, reset_mask=reset_mask)
+
+  def mark_reset(self, mask):
+    """Per-lane reset marks (base.Environment.mark_reset): the lanes with mask[i] != 0 reset at their next call."""
+    return self._env.mark_reset(mask)
 
   def rollout(self, actions):
     return self._env.rollout(actions)
@@ -235,8 +241,8 @@ class Logging(_RewardWrapper):
     self._forward_new_rows()
     return timestep
 
-  def step(self, action):
-    timestep = self._env.step(action)
+  def step(self, action, reset_mask=None):
+    timestep = self._env.step(action) if reset_mask is None else self._env.step(action, reset_mask=reset_mask)
     self._forward_new_rows()
     return timestep
 
@@ -468,8 +474,8 @@ class ImageObservation(dm_env.EnvironmentBase):
   def reset(self):
     return self._convert(self._env.reset())
 
-  def step(self, action):
-    return self._convert(self._env.step(action))
+  def step(self, action, reset_mask=None):
+    return self._convert(self._env.step(action) if reset_mask is None else self._env.step(action, reset_mask=reset_mask))
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

@@ -548,6 +548,21 @@ int bsx_abi_version(void);
  * episode_return.  Asynchronous on hip_stream like every entry point; info_out may not alias info. */
 int bsx_bsuite_info(int32_t family, int32_t variant, int64_t n_lanes, const int32_t* state, const double* info,
                     int32_t n_info, int32_t folded, double* info_out, void* hip_stream);
+/* Per-lane reset (v12): marks every lane i with mask[i] != 0 so that its NEXT call — a step, or the first step of a
+ * rollout — does what an explicit reset() (call->force_reset) does for the whole batch: a FIRST TimeStep, the action
+ * ignored, the reset draws of that call's index, the running episode abandoned.  One small launch, one byte of mask per
+ * lane; it draws nothing, reads no call index and bumps no counter, so an all-zero mask leaves a run bit for bit as it
+ * was.  `state` is the column that carries the family's reset_next bit: the packed state column, or the `steps` column
+ * of cartpole / mountain_car.  `folded` != 0 (the `folded` of bsx_bsuite_info: columns maintained without
+ * call->logging): classic cartpole (variant 0) and mountain_car add the k rewards the abandoned episode has paid to
+ * info column 0 (+k / -k), as their forced reset does; every other case leaves `info` alone and it may be NULL.  A lane
+ * that resets anyway (fresh, after LAST, marked before) is not written: marking twice is marking once.  Unmasked lanes
+ * are not written.  Asynchronous on hip_stream, no allocation, no synchronisation, graph-capturable.  Do not mark the
+ * lanes of a segment between the two launches of a pipelined pair of groups (they hold a second state column).
+ * BSX_EINVAL: family outside BSX_FAM_DEEP_SEA .. BSX_FAM_MNIST, n_lanes < 0; BSX_ENULL: mask or state NULL, info NULL
+ * where the family folds; n_lanes == 0: returns 0 without a launch. */
+int bsx_lane_reset_mark(int32_t family, int32_t variant, int64_t n_lanes, const uint8_t* mask, int32_t* state,
+                        double* info, int32_t folded, void* hip_stream);
 /* Bytes of bsx_call_t.row_scratch for `n_lanes` lanes of a `family` (BSX_FAM_*) observation row of `obs_numel` floats:
  * PLANES bit planes of ceil(n_lanes / 64) * 2 * obs_numel uint32 (memory_chain 2, umbrella_chain 1) + one f32 column
  * [n_lanes] per genuine float of the row (memory_chain 2: time, query; umbrella_chain 1: time).  0 = this family / row
