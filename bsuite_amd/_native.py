@@ -104,6 +104,13 @@ class CatchCfg(ctypes.Structure):
   _fields_ = [('rows', ctypes.c_int32), ('columns', ctypes.c_int32)]
 
 
+class Policy(ctypes.Structure):
+  """bsx_policy_t: the tabular policy of bsx_<family>_policy_rollout."""
+  _fields_ = [('table', ctypes.c_void_p), ('n_states', ctypes.c_int32), ('n_policies', ctypes.c_int32),
+              ('policy_index', ctypes.c_void_p), ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64),
+              ('actions_out', ctypes.c_void_p)]
+
+
 class BanditCfg(ctypes.Structure):
   _fields_ = [('num_actions', ctypes.c_int32), ('_pad', ctypes.c_int32),
               ('rewards', ctypes.c_double * BANDIT_MAX_ACTIONS)]
@@ -179,6 +186,10 @@ _SIGS = {
                           ctypes.c_int),
     'bsx_catch_step': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                        ctypes.c_int),
+    'bsx_deep_sea_policy_rollout': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
+                                     TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_catch_policy_rollout': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
+                                  TimeStepPtrs, _P], ctypes.c_int),
     'bsx_bandit_step': ([ctypes.POINTER(BanditCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                         ctypes.c_int),
     'bsx_memory_chain_step': ([ctypes.POINTER(MemoryChainCfg), ctypes.POINTER(Call), _P, _P, _P,

@@ -12,6 +12,7 @@
 #include "../../include/bsuite_amd.h"
 #include "../../include/bsx_stream.h"
 #include "bsx_index.h"
+#include "bsx_policy.h"
 
 #define BSX_BLOCK 256
 #define BSX_WAVE 64
@@ -569,6 +570,97 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_index_rollout_kernel(const type
   }
   bsx_final_barrier();
   bsx_flush_counts(a.ctl, s_cnt, block_id & (BSX_COUNTER_SHARDS - 1));    // (the shard is all bsx_flush_counts takes from it)
+}
+
+// The tabular policy of a fused closed-loop rollout, flattened out of bsx_policy_t on the host.
+struct bsx_policy_args {
+  const uint8_t* table;          // [n_policies, n_states]
+  const int32_t* policy_index;   // [n_lanes], nullptr when n_policies == 1
+  int32_t* actions_out;          // [n_steps, n_lanes]
+  double epsilon;
+  uint64_t explore_seed;
+  int32_t n_states, n_policies;
+  uint32_t num_actions;
+  int32_t in_lds;                // one shared table of at most BSX_POLICY_LDS_BYTES: every workgroup stages it in LDS
+};
+
+// rollout_policy(T) in index mode: bsx_index_rollout_kernel with the action SOURCE replaced — no action tensor is read; the
+// lane's action is the entry of a uint8 table at the key of the observation the lane is about to leave, decoded by HotFn
+// from the state word the thread holds in a register anyway (bsx_policy.h has the key and the selection rule).  A shared
+// table sits in LDS next to the family's own tables; a population of tables (and a table too large for LDS) is read from
+// global memory, one byte per lane-step, L2-resident.  epsilon is uniform per launch: epsilon == 0 executes no Philox.
+// The chosen actions are an output column like the others: [T,B], non-temporal.  Everything else — Fam::stage once, LAST /
+// FIRST counted per thread and pooled once, the output policies of a rollout — is the index rollout's.
+template <class Fam, class HotFn>
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_policy_rollout_kernel(const typename Fam::args a, const int n_steps,
+                                                                             int32_t* __restrict__ rows, const HotFn fn,
+                                                                             const bsx_policy_args p) {
+  __shared__ typename Fam::shared s_fam;
+  __shared__ unsigned int s_cnt[2];
+  __shared__ uint8_t s_tab[BSX_POLICY_LDS_BYTES];
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  Fam::stage(a, s_fam);
+  const int S = p.n_states;
+  const bool in_lds = p.in_lds != 0;                                      // uniform
+  if (in_lds) {
+    for (int k = threadIdx.x; k < S; k += BSX_BLOCK) s_tab[k] = p.table[k];
+  }
+  __syncthreads();
+  const int64_t B = a.ctl.n_lanes;
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  const bool mine = i < B;
+  const uint64_t lane = a.ctl.lane_offset + (uint64_t)i;
+  const uint64_t step0 = bsx_step_of(a.ctl);
+  const bool explore = p.epsilon > 0.0;                                   // uniform
+  int32_t st = mine ? a.state[i] : 0;
+  // the lane's own table (a population: its row, clamped — a bad index cannot fault)
+  const uint8_t* __restrict__ tab = p.table;
+  if (mine && p.policy_index != nullptr) tab += (int64_t)bsx_policy_clamp(p.policy_index[i], p.n_policies) * S;
+  uint32_t n_last = 0, n_first = 0;
+  uint32_t block_id = blockIdx.x;                                         // (in a vector register: see bsx_index_rollout_kernel)
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(block_id));
+#endif
+  if (mine) {
+#pragma unroll 1
+    for (int t = 0; t < n_steps; ++t) {
+      const uint64_t step = step0 + (uint64_t)t;
+      const int64_t oi = (int64_t)t * B + i;
+      const int key = bsx_policy_clamp(fn.policy_key(st), S);
+      // (two loads in two branches, kept apart by the empty asm: merged into one load through a generic pointer the lookup
+      // would be a flat_load, which counts against vmcnt as well — the wait for it would drain the step's stores every step)
+      uint32_t entry;
+      if (in_lds) {
+        entry = s_tab[key];
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(entry));
+#endif
+      } else {
+        entry = tab[key];
+      }
+      uint32_t w0 = 0, w1 = 0, w2 = 0;
+      if (explore) {
+        const bsx_u32x4 w = bsx_policy_draws(p.explore_seed, lane, step);
+        w0 = w.v[0]; w1 = w.v[1]; w2 = w.v[2];
+      }
+      const int act = bsx_policy_select(entry, Fam::resets(st), p.epsilon, w0, w1, w2, p.num_actions);
+      int32_t nst; double reward;
+      const int type = Fam::template advance<true>(a, s_fam, i, lane, step, st, act, nst, reward);
+      st = nst;
+      bsx_emit_at<0, 0, false, -1, BSX_OUT_SCALARS.rollout>(a.ctl, a.out, i, oi, lane, step, type, reward);
+      bsx_index_store<BSX_OUT_INDEX.rollout>(rows, oi, nst, fn);
+      bsx_st<BSX_OUT_SCALARS.rollout>(&p.actions_out[oi], (int32_t)act);
+      n_last += type == BSX_LAST ? 1u : 0u;
+      n_first += type == BSX_FIRST ? 1u : 0u;
+    }
+    a.state[i] = st;
+  }
+  if (a.ctl.counters != nullptr) {
+    if (n_last) atomicAdd(&s_cnt[0], n_last);
+    if (n_first) atomicAdd(&s_cnt[1], n_first);
+  }
+  bsx_final_barrier();
+  bsx_flush_counts(a.ctl, s_cnt, block_id & (BSX_COUNTER_SHARDS - 1));
 }
 
 // n / cells for n < 2^20 via the host-built magic (bsx_div_magic); cells == 1 has no 32-bit magic.

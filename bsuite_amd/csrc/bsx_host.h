@@ -291,6 +291,48 @@ static inline int bsx_launch_status() { return (int)hipGetLastError(); }
 int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes, int32_t family, int32_t p0, int32_t p1,
                             bool rollout, hipStream_t st);
 
+// The refusals of bsx_<family>_policy_rollout that do not depend on the family, in the documented order (include/bsuite_amd.h):
+// modes, scalars, then — for a call with lanes — pointers.  `n_states`: the family's table length for this cfg.
+static inline int bsx_check_policy_call(const bsx_call_t* call, const bsx_policy_t* pol, int32_t n_states, const int32_t* state,
+                                        const bsx_timestep_t& out, const double* info) {
+  if (call == nullptr || pol == nullptr) return BSX_ENULL;
+  if ((call->flags & (BSX_CALL_OBS_MASK | BSX_CALL_OBS_INDEX)) != BSX_CALL_OBS_INDEX) return BSX_EMODE;
+  if (call->logging != nullptr || call->wrap.kind != BSX_WRAP_NONE || call->stream.mt_state != nullptr ||
+      call->stream.mt_pos != nullptr || call->reward_f64 != nullptr || call->obs_paint != nullptr ||
+      call->state_alt != nullptr || call->action_ring > 1 || call->force_reset)
+    return BSX_EMODE;
+  if (call->n_steps < 1 || call->n_lanes < 0 || call->n_lanes > ((int64_t)1 << 40)) return BSX_EINVAL;
+  if (pol->n_states != n_states || pol->n_policies < 1) return BSX_EINVAL;
+  if (!(pol->epsilon >= 0.0 && pol->epsilon <= 1.0)) return BSX_ERANGE;      // (NaN included)
+  if (call->n_lanes == 0) return 0;
+  if (pol->table == nullptr || pol->actions_out == nullptr || state == nullptr || info == nullptr ||
+      out.reward == nullptr || out.discount == nullptr || out.step_type == nullptr || out.observation == nullptr)
+    return BSX_ENULL;
+  if (pol->n_policies > 1 && pol->policy_index == nullptr) return BSX_ENULL;
+  if ((reinterpret_cast<uintptr_t>(out.observation) & 15u) != 0) return BSX_EALIGN;
+  return 0;
+}
+
+// Launches bsx_policy_rollout_kernel: `a` from the family's make() (its action pointer is never read).
+template <class Fam, class HotFn>
+static int bsx_policy_rollout_call(const typename Fam::args& a, const bsx_call_t* call, const bsx_policy_t* pol,
+                                   uint32_t num_actions, bsx_timestep_t out, const HotFn& fn) {
+  const int64_t blocks = (call->n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
+  bsx_policy_args p;
+  p.table = pol->table;
+  p.policy_index = pol->n_policies > 1 ? pol->policy_index : nullptr;
+  p.actions_out = pol->actions_out;
+  p.epsilon = pol->epsilon;
+  p.explore_seed = pol->explore_seed;
+  p.n_states = pol->n_states; p.n_policies = pol->n_policies;
+  p.num_actions = num_actions;
+  p.in_lds = (pol->n_policies == 1 && pol->n_states <= BSX_POLICY_LDS_BYTES) ? 1 : 0;
+  bsx_policy_rollout_kernel<Fam, HotFn><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)call->hip_stream>>>(
+      a, call->n_steps, reinterpret_cast<int32_t*>(out.observation), fn, p);
+  return bsx_launch_status();
+}
+
 // One call of a two-kernel family (deep_sea, catch): step() / reset() / a rollout of T steps with outputs
 // [T,B,...].  `a` comes from the family's make(); K = stores per thread of its observation stream.
 //   delta mode (obs_paint)          one launch per step: advance + in-place patch

@@ -37,6 +37,20 @@ extern "C" int bsx_catch_step(const bsx_catch_t* cfg, const bsx_call_t* call, co
   return bsx_pair_call<catch_fam, catch_hot, 2>(a, call, action, state, out, cells, catch_hot{cfg->rows, cfg->columns});
 }
 
+extern "C" int bsx_catch_policy_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                                        int32_t* state, bsx_timestep_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  if (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) return BSX_ERANGE;
+  int rc = bsx_check_policy_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  catch_fam::args a;
+  // (the action pointer of a policy rollout is never read: actions_out stands in for it in the common checks)
+  rc = catch_make(cfg, call, policy->actions_out, state, out, info, &a);
+  if (rc != 0) return rc;
+  a.action = nullptr;
+  return bsx_policy_rollout_call<catch_fam, catch_hot>(a, call, policy, 3u, out, catch_hot{cfg->rows, cfg->columns});
+}
+
 extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catch_t* cfg, const bsx_call_t* call,
                                    const int32_t* action, int32_t* state, bsx_timestep_t out, double* info) {
   if (g == nullptr) return BSX_ENULL;

@@ -81,6 +81,8 @@ struct catch_fam {
                                                      int32_t st, int act, int32_t& nst, double& reward) {
     return advance<LEAN, NOMT>(a, s, i, lane, step, st, act, nst, reward);
   }
+  // does the lane reset on its next call (the test advance() makes, without force_reset)?
+  __device__ static __forceinline__ bool resets(int32_t st) { return (st & CATCH_RESET_BIT) != 0; }
 };
 
 struct catch_hot {
@@ -92,6 +94,12 @@ struct catch_hot {
   __device__ __forceinline__ void operator()(int32_t st, int& a, int& b) const {
     a = ((st >> 8) & 0xFF) * cols + (st & 0xFF);          // ball   (catch.py:111)
     b = (rows - 1) * cols + ((st >> 16) & 0xFF);          // paddle (catch.py:112)
+  }
+  // key of the lane's observation in a tabular policy (bsx_policy.h)
+  __device__ __forceinline__ int policy_key(int32_t st) const {
+    int a, b;
+    (*this)(st, a, b);
+    return bsx_policy_key_catch(a, b, rows, cols);
   }
 };
 

@@ -189,6 +189,20 @@ extern "C" int bsx_deep_sea_step(const bsx_deep_sea_t* cfg, const bsx_call_t* ca
   return bsx_pair_call<deep_sea_fam, deep_sea_hot, 4>(a, call, action, state, out, cells, deep_sea_hot{cfg->size});
 }
 
+extern "C" int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                                           int32_t* state, bsx_timestep_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  if (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) return BSX_ERANGE;
+  int rc = bsx_check_policy_call(call, policy, bsx_policy_states_deep_sea(cfg->size), state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  deep_sea_fam::args a;
+  // (the action pointer of a policy rollout is never read: actions_out stands in for it in the common checks)
+  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &a);
+  if (rc != 0) return rc;
+  a.action = nullptr;
+  return bsx_policy_rollout_call<deep_sea_fam, deep_sea_hot>(a, call, policy, 2u, out, deep_sea_hot{cfg->size});
+}
+
 extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_deep_sea_t* cfg,
                                       const bsx_call_t* call, const int32_t* action, int32_t* state,
                                       bsx_timestep_t out, double* info) {

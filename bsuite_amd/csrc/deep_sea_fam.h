@@ -98,6 +98,8 @@ struct deep_sea_fam {
                                                      int32_t st, int act, int32_t& nst, double& reward) {
     return advance<LEAN, -1, NOMT>(a, s, i, lane, step, st, act, nst, reward);
   }
+  // does the lane reset on its next call (the test advance() makes, without force_reset)?
+  __device__ static __forceinline__ bool resets(int32_t st) { return (st & DS_RESET_BIT) != 0; }
 };
 
 // hot cell of a lane from its packed state (observation stream kernel)
@@ -111,6 +113,12 @@ struct deep_sea_hot {
     const int row = st & 0xFF, col = (st >> 8) & 0xFF;
     a = row < N ? row * N + col : -1;     // deep_sea.py:105-107 (terminal observation is all-zero)
     b = -1;
+  }
+  // key of the lane's observation in a tabular policy (bsx_policy.h)
+  __device__ __forceinline__ int policy_key(int32_t st) const {
+    int a, b;
+    (*this)(st, a, b);
+    return bsx_policy_key_deep_sea(a);
   }
 };
 

@@ -865,11 +865,16 @@ static void launch_regs_rollout(const typename Env::args& a, int n_steps, int v,
   if constexpr (Env::HAS_REGS) {
     constexpr bool HB = small_obs_has_big<Env>();
     constexpr int V1 = small_obs_v1<Env>();
-    const bool tab = Env::table_fits(a);
+    // (a family without a table — TABLE_MAX_BYTES = 0: bandit, discounting_chain, whose table_fits() is the constant false —
+    // has no TAB instantiation at all: a kernel that can never launch still counts against the library's kernel budget)
+    constexpr bool HT = Env::TABLE_MAX_BYTES > 0;
+    const bool tab = HT && Env::table_fits(a);
 #define REGS_ROLLOUT(BIGV, VV)                                                                                     \
     {                                                                                                              \
-      if (tab) small_obs_lean_rollout_kernel<Env, BIGV, VV, true><<<g, b, lds, st>>>(a, n_steps);                  \
-      else small_obs_lean_rollout_kernel<Env, BIGV, VV, false><<<g, b, lds, st>>>(a, n_steps);                     \
+      if constexpr (HT) {                                                                                          \
+        if (tab) small_obs_lean_rollout_kernel<Env, BIGV, VV, true><<<g, b, lds, st>>>(a, n_steps);                \
+      }                                                                                                            \
+      if (!tab) small_obs_lean_rollout_kernel<Env, BIGV, VV, false><<<g, b, lds, st>>>(a, n_steps);                \
     }
     if (v == 1 && big) REGS_ROLLOUT(HB, V1)
     else if (v == 1) REGS_ROLLOUT(false, V1)

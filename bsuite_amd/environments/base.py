@@ -23,6 +23,7 @@ for the reference's run loop, which holds `timestep` and `new_timestep`
 There is no CPU fallback: without a HIP device the first reset()/step() raises.
 """
 import contextlib
+import ctypes
 import secrets
 from typing import Any, Dict, Optional
 
@@ -769,6 +770,116 @@ class Environment(dm_env.EnvironmentBase):
     self._step_index += T
     return dm_env.TimeStep(step_type=out['step_type'], reward=out['reward'], discount=out['discount'],
                            observation=out['observation'])
+
+  _policy_abi = None   # subclass: the C-ABI entry point of rollout_policy (deep_sea, catch)
+
+  @property
+  def policy_num_states(self) -> int:
+    """Entries of one table of `rollout_policy` (deep_sea: N * N, catch: rows * columns * columns)."""
+    raise ValueError(f'{type(self).__name__} has no tabular policy rollout (deep_sea and catch only)')
+
+  def _check_rollout_policy(self, policy, num_steps, policy_index, epsilon, explore_seed):
+    """The refusals of rollout_policy(): all of them before any GPU use, nothing allocated."""
+    name = type(self).__name__
+    if self._policy_abi is None:
+      raise ValueError(f'{name} has no tabular policy rollout (deep_sea and catch only)')
+    if self._scalar:
+      raise ValueError('rollout_policy() needs the batched view (batch=B)')
+    if not self._index:
+      raise ValueError(f"rollout_policy() looks its actions up by the index observation: build the environment with "
+                       f"observation_mode='index' (this one is {self.observation_mode!r}, {self._obs_dtype})")
+    if self._rng_mode != 'philox':
+      raise ValueError("rollout_policy() needs the counter-based draw stream (rng='philox')")
+    if self._logging is not None:
+      raise ValueError('rollout_policy() is not available with Logging enabled')
+    if self._wrap[0] != _native.WRAP_NONE:
+      raise ValueError('rollout_policy() is not available under a reward wrapper')
+    if getattr(self, '_grouped_by', None) is not None:
+      raise RuntimeError('rollout_policy() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
+    if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
+      raise ValueError(f'rollout_policy: num_steps must be an integer >= 1, got {num_steps!r}')
+    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
+      raise ValueError(f'rollout_policy: epsilon must be a number in [0, 1], got {epsilon!r}')
+    if isinstance(explore_seed, bool) or not isinstance(explore_seed, (int, np.integer)) or not 0 <= int(explore_seed) < (1 << 64):
+      raise ValueError(f'rollout_policy: explore_seed must be an integer in [0, 2^64), got {explore_seed!r}')
+    S = self.policy_num_states
+    if (not torch.is_tensor(policy) or policy.dtype != torch.uint8 or policy.device != self._device or policy.dim() not in (1, 2)
+        or int(policy.shape[-1]) != S or policy.numel() == 0 or not policy.is_contiguous()):
+      raise ValueError(f'rollout_policy: policy must be a contiguous uint8 tensor of shape ({S},) or (P, {S}) on {self._device}')
+    P = 1 if policy.dim() == 1 else int(policy.shape[0])
+    if P == 1:
+      if policy_index is not None:
+        raise ValueError('rollout_policy: policy_index names the row of a population of tables; with one table it must be None')
+    elif (not torch.is_tensor(policy_index) or policy_index.dtype != torch.int32 or policy_index.device != self._device
+          or tuple(policy_index.shape) != (self._batch,) or not policy_index.is_contiguous()):
+      raise ValueError(f'rollout_policy: a population of {P} tables needs policy_index, a contiguous int32 tensor of shape '
+                       f'({self._batch},) on {self._device}')
+    return P
+
+  def rollout_policy(self, policy, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """A closed-loop rollout of `num_steps` steps in ONE launch, the actions looked up in a table by the lane's own
+    observation (DeepSea and Catch, batched view, observation_mode='index', counter-based draws, no wrapper).
+
+    policy: uint8 device tensor [S] (one table for all lanes) or [P, S] (a population; `policy_index`, int32 [B], names
+    each lane's row and is clamped to [0, P-1]); S = `policy_num_states`; entry k is the action taken when the lane's
+    observation has key k (utils.observations.policy_key).  Returns `(ts, actions)`: `ts` as rollout() returns it
+    ([T,B] step_type / reward / discount, [T,B,K] int32 observation) and `actions` int32 [T,B], the actions taken.  The
+    result equals, bit for bit,
+
+        for t in range(T): a = 0 where the lane resets on this call, else policy[row, key(observation before the call)]
+                           step(a)
+
+    — a lane resets when it is fresh, after LAST, or marked by mark_reset(); actions[t] is 0 there.  A table entry outside
+    the action_spec behaves as the same value passed to step().  With epsilon > 0 a lane that does not reset draws U()
+    and, if U < epsilon, takes RandInt(num_actions) instead: stream 2 of (explore_seed, global lane id, call index)
+    (include/bsx_stream.h); the environment's own draws are untouched.  State, info, counters and the call index are
+    left as T step() calls leave them; calls interleave freely with step / rollout / mark_reset / reset.  Output buffers
+    are cached per T and overwritten by the next call of the same T."""
+    P = self._check_rollout_policy(policy, num_steps, policy_index, epsilon, explore_seed)
+    if torch.cuda.is_available() and torch.cuda.current_device() != self._device.index:
+      with torch.cuda.device(self._device):
+        return self.rollout_policy(policy, num_steps, policy_index=policy_index, epsilon=epsilon, explore_seed=explore_seed)
+    self._ensure_allocated()
+    T = int(num_steps)
+    cache = self.__dict__.setdefault('_policy_rollout_out', {})
+    if T not in cache:
+      B, dev = self._batch, self._device
+      o = dict(reward=torch.empty((T, B), dtype=torch.float32, device=dev),
+               discount=torch.empty((T, B), dtype=torch.float32, device=dev),
+               step_type=torch.empty((T, B), dtype=torch.int8, device=dev),
+               observation=torch.empty((T, B) + self._obs_shape, dtype=self._obs_dtype, device=dev),
+               actions=torch.empty((T, B), dtype=torch.int32, device=dev))
+      cache[T] = (o, _native.TimeStepPtrs(o['reward'].data_ptr(), o['discount'].data_ptr(),
+                                          o['step_type'].data_ptr(), o['observation'].data_ptr()))
+    out, ptrs = cache[T]
+    pol = _native.Policy(policy.data_ptr(), self.policy_num_states, P,
+                         policy_index.data_ptr() if policy_index is not None else None,
+                         float(epsilon), int(explore_seed), out['actions'].data_ptr())
+    call = self._call_desc
+    call.force_reset = 0
+    call.n_steps = T
+    call.state_alt = None
+    hip_stream = torch.cuda.current_stream(self._device).cuda_stream
+    call.hip_stream = hip_stream
+    fn = getattr(_native.lib, self._policy_abi)
+    args = (ctypes.byref(self._cfg), ctypes.byref(call), ctypes.byref(pol), self._state['state'].data_ptr(), ptrs,
+            self._info.data_ptr())
+    try:
+      if self._device_step_counter:
+        call.stream.step_index = 0
+        rc = fn(*args)
+        if rc == 0 and self._shared_step_counter is None:
+          rc = _native.lib.bsx_counter_add(self._step_base.data_ptr(), T, hip_stream)
+      else:
+        call.stream.step_index = self._step_index
+        rc = fn(*args)
+    finally:
+      call.n_steps = 0
+    if rc != 0:
+      _native.check(rc, f'{type(self).__name__} rollout_policy')
+    self._step_index += T
+    return (dm_env.TimeStep(step_type=out['step_type'], reward=out['reward'], discount=out['discount'],
+                            observation=out['observation']), out['actions'])
 
   def _step(self, action):
     raise NotImplementedError('The batched engine fuses _step/_reset into one kernel; call step().')

@@ -49,6 +49,13 @@ class Catch(base.Environment):
   def _native_args(self, call, action_ptr, out):
     return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())
 
+  _policy_abi = 'bsx_catch_policy_rollout'
+
+  @property
+  def policy_num_states(self) -> int:
+    """Entries of one table of `rollout_policy`: key ball_cell * columns + paddle_x (utils.observations.policy_key)."""
+    return self._rows * self._columns * self._columns
+
   def _check_scalar_action(self, action):
     _ACTIONS[action]  # IndexError exactly where catch.py:84 raises it  pylint: disable=pointless-statement
 

@@ -83,6 +83,13 @@ class DeepSea(base.Environment):
   def _native_args(self, call, action_ptr, out):
     return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())
 
+  _policy_abi = 'bsx_deep_sea_policy_rollout'
+
+  @property
+  def policy_num_states(self) -> int:
+    """Entries of one table of `rollout_policy`: one per cell, key row * N + column."""
+    return self._size * self._size
+
   @property
   def optimal_return(self):
     return self._optimal_return

@@ -33,6 +33,25 @@ def index_to_dense(index: torch.Tensor, board_shape: Sequence[int], dtype: torch
   return out
 
 
+def policy_key(index_rows: torch.Tensor, board_shape: Sequence[int]) -> torch.Tensor:
+  """The key `[...]` (int64) of an index observation `[..., K]` in a tabular policy (`env.rollout_policy`): the entry of
+  the table a lane with that observation takes its action from.
+
+    deep_sea (K = 1)  the observation itself, `row * N + col`; -1 on the terminal observation, which is never looked up
+                      (the lane resets on the call that follows it);
+    catch    (K = 2)  `ball_cell * columns + paddle_x` with `paddle_x = paddle_cell - (rows - 1) * columns`.
+
+  A table has `env.policy_num_states` entries: N * N, or rows * columns * columns."""
+  rows, columns = (int(s) for s in board_shape)
+  k = int(index_rows.shape[-1])
+  idx = index_rows.to(torch.int64)
+  if k == 1:
+    return idx[..., 0]
+  if k == 2:
+    return idx[..., 0] * columns + (idx[..., 1] - (rows - 1) * columns)
+  raise ValueError(f'policy_key: index observations have one (deep_sea) or two (catch) entries, got {k}')
+
+
 def index_embedding(index: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
   """`sum_k table[index[..., k] + 1]`: the gather form of `board.reshape(..., cells) @ W` for a one-hot board, with
   `table` = `[cells + 1, D]` whose row 0 is zero (the row -1 selects) and whose row c + 1 is `W[c]`.  For catch the two

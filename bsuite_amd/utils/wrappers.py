@@ -65,6 +65,13 @@ class _RewardWrapper(dm_env.EnvironmentBase):
   def rollout(self, actions):
     return self._env.rollout(actions)
 
+  def rollout_policy(self, policy, num_steps, **kwargs):
+    """Refused: the fused policy rollout runs the raw environment's kernel, without this wrapper's epilogue
+    (base.Environment.rollout_policy).  Delegating would drop the wrapper silently."""
+    del policy, num_steps, kwargs
+    raise ValueError(f'rollout_policy() is not available through {type(self).__name__}: the fused policy rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -476,6 +483,12 @@ class ImageObservation(dm_env.EnvironmentBase):
 
   def step(self, action, reset_mask=None):
     return self._convert(self._env.step(action) if reset_mask is None else self._env.step(action, reset_mask=reset_mask))
+
+  def rollout_policy(self, policy, num_steps, **kwargs):
+    """Refused: a fused policy rollout returns index observations, never images (base.Environment.rollout_policy)."""
+    del policy, num_steps, kwargs
+    raise ValueError('rollout_policy() is not available through ImageObservation: the fused policy rollout returns index '
+                     'observations; call it on an un-wrapped DeepSea / Catch')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

@@ -2,7 +2,7 @@
 reads the observation tensor the engine just wrote — no host round trip anywhere in the loop.
 
     python examples/closed_loop_policy.py [bsuite_id] [lanes] [steps] [--observation-dtype float32|uint8|float16|bfloat16]
-                                          [--observation-mode dense|index]
+                                          [--observation-mode dense|index] [--fused-table]
 
 With a narrow --observation-dtype (deep_sea, catch) the engine writes the boards as bytes or 16-bit floats, and the policy
 converts each board once, as it reads it: to float32 from uint8, not at all from float16 / bfloat16, whose weights and
@@ -12,6 +12,11 @@ With --observation-mode index (deep_sea, catch) the engine writes the numbers of
 board, and the same linear policy is a row gather: `board @ W` of a one-hot board is `W[cell]` (summed over the ball's and
 the paddle's cell for catch; a cell they share counts once, as on the board) — the same float32 logits as the dense run
 for the same weights, without the board ever being written or read.
+
+With --fused-table (deep_sea, catch; implies --observation-mode index) the same greedy policy is tabulated once — entry k
+of a uint8 table is the argmax of the logits of the observation with key k (`observations.policy_key`) — and the whole
+loop runs inside the engine: `env.rollout_policy(table, T)` is ONE launch for T closed-loop steps, and gives the same
+trajectories (the same bsuite_info sums) as the eager index run.
 
 This is the batched counterpart of the reference run loop (bsuite/baselines/experiment.py:43-57):
 `timestep = env.step(agent.select_action(timestep))`, with 2^20 environments per call.
@@ -36,7 +41,10 @@ def main():
   ap.add_argument('steps', nargs='?', type=int, default=200)
   ap.add_argument('--observation-dtype', default='float32', choices=('float32', 'uint8', 'float16', 'bfloat16'))
   ap.add_argument('--observation-mode', default='dense', choices=('dense', 'index'))
+  ap.add_argument('--fused-table', action='store_true', help='tabulate the greedy policy and run the loop inside the engine (rollout_policy)')
   a = ap.parse_args()
+  if a.fused_table:
+    a.observation_mode = 'index'
   bsuite_id, lanes, steps = a.bsuite_id, a.lanes, a.steps
   index = a.observation_mode == 'index'
   env = bsuite_amd.load_from_id(bsuite_id, batch=lanes, seed=0, observation_dtype=a.observation_dtype,
@@ -61,17 +69,34 @@ def main():
   def policy(timestep):                           # greedy
     return logits_of(timestep).argmax(dim=1).to(torch.int32)
 
+  def greedy_table():                             # entry k: the action `policy` takes on the observation with key k
+    rows, columns = env.board_shape
+    k = torch.arange(env.policy_num_states, device='cuda')
+    if env.observation_spec().shape[0] == 1:      # deep_sea: the key is the cell
+      cells = k[:, None].to(torch.int32)
+    else:                                         # catch: key = ball_cell * columns + paddle_x
+      cells = torch.stack([k // columns, (rows - 1) * columns + k % columns], dim=1).to(torch.int32)
+    return policy(ts._replace(observation=cells)).to(torch.uint8)
+
   ts = env.reset()
-  for _ in range(20):
-    ts = env.step(policy(ts))
-  torch.cuda.synchronize()
-  t0 = time.perf_counter()
-  for _ in range(steps):
-    ts = env.step(policy(ts))
+  if a.fused_table:
+    fused = greedy_table()
+    env.rollout_policy(fused, 20)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for n in [32] * (steps // 32) + ([steps % 32] if steps % 32 else []):
+      env.rollout_policy(fused, n)
+  else:
+    for _ in range(20):
+      ts = env.step(policy(ts))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+      ts = env.step(policy(ts))
   torch.cuda.synchronize()
   dt = time.perf_counter() - t0
   info = {k: float(v.sum()) for k, v in env.bsuite_info().items()}
-  print(json.dumps(dict(bsuite_id=bsuite_id, observation_dtype=a.observation_dtype, observation_mode=a.observation_mode, lanes=lanes, steps=steps, ms_per_step=round(dt / steps * 1e3, 4),
+  print(json.dumps(dict(bsuite_id=bsuite_id, observation_dtype=a.observation_dtype, observation_mode=a.observation_mode, fused_table=a.fused_table, lanes=lanes, steps=steps, ms_per_step=round(dt / steps * 1e3, 4),
                         env_steps_per_s=round(lanes * steps / dt), episodes_finished=int(env.episode_counters()[0]),
                         bsuite_info_sums=info)))
 

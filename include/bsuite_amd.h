@@ -287,6 +287,43 @@ typedef struct {
 int bsx_catch_step(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action,
                    int32_t* state, bsx_timestep_t out, double* info);
 
+/* ---- fused closed-loop rollouts from a tabular policy (deep_sea, catch; v12, additive) ---------
+ * The third action source, next to the action tensor and the action ring: n_steps consecutive step() calls in ONE launch
+ * whose actions are looked up, inside the kernel, in a table indexed by the lane's own index observation — the run loop
+ * of bsuite/baselines/experiment.py:43-57 for an agent whose policy is a table.  Per step t = 0 .. n_steps-1 and lane i:
+ *     a = 0                                   if the lane resets on this call (fresh, after LAST, or marked by
+ *                                             bsx_lane_reset_mark: the reset_next bit of its state word)
+ *       = RandInt(num_actions)                else if epsilon > 0 and U() < epsilon
+ *       = table[row(i) * n_states + key]      else, key = the observation BEFORE the call:
+ *                                               deep_sea  row * N + column                       (n_states = N * N)
+ *                                               catch     ball_cell * columns + paddle_x         (n_states = rows * columns^2)
+ *     then exactly step(a); actions_out[t * n_lanes + i] = a.
+ * row(i) = 0 when n_policies == 1, else policy_index[i] clamped to [0, n_policies - 1].  U() and RandInt come from stream
+ * BSX_STREAM_POLICY of (explore_seed, global lane id, the step's call index) — include/bsx_stream.h; the environment's
+ * own stream is untouched, so the trajectory is the one bsx_<family>_step gives for the same actions.  A table entry
+ * outside the action_spec behaves as that value passed to step() (catch: clipped and counted in the error word).
+ * `call` is that of a rollout in index mode: n_steps >= 1 (1 is allowed here), flags with BSX_CALL_OBS_INDEX and element
+ * code 0, outputs [n_steps, n_lanes] / [n_steps, n_lanes, K] int32; state, info, counters and the call index end up as
+ * n_steps step() calls leave them.
+ * BSX_EMODE (all refusals come before any device work): the flags' observation bits are not exactly BSX_CALL_OBS_INDEX;
+ * logging, a reward wrapper, MT19937 columns, reward_f64, obs_paint, state_alt, an action ring or force_reset is set.
+ * BSX_EINVAL: n_steps < 1, n_lanes < 0, n_states other than the family's, n_policies < 1.  BSX_ERANGE: epsilon outside
+ * [0, 1] (or NaN), cfg outside the family's range.  BSX_ENULL: a null pointer, policy_index included when
+ * n_policies > 1.  n_lanes == 0 returns 0 and launches nothing.  Asynchronous on call->hip_stream, no allocation, no
+ * synchronisation, graph-capturable. */
+typedef struct {
+  const uint8_t* table;        /* device [n_policies, n_states]                                  */
+  int32_t n_states, n_policies;
+  const int32_t* policy_index; /* device [n_lanes] or NULL when n_policies == 1                  */
+  double epsilon;
+  uint64_t explore_seed;
+  int32_t* actions_out;        /* device [n_steps, n_lanes]                                      */
+} bsx_policy_t;
+int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                                int32_t* state, bsx_timestep_t out, double* info);
+int bsx_catch_policy_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                             int32_t* state, bsx_timestep_t out, double* info);
+
 /* ---- bandit : bsuite/environments/bandit.py:35-73 ----------------------------------------- */
 #define BSX_BANDIT_MAX_ACTIONS 32
 typedef struct {

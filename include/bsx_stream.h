@@ -14,7 +14,12 @@
  *               counter = (lane[31:0], lane[63:32], step[31:0],
  *                          step[47:32]<<16 | stream_id<<8 | block)
  *               word w of a (lane, step, stream) triple = output word (w & 3) of block (w >> 2).
- *   stream_id : 0 = environment dynamics (`env._rng`), 1 = reward wrapper (`RewardNoise._rng`).
+ *   stream_id : 0 = environment dynamics (`env._rng`), 1 = reward wrapper (`RewardNoise._rng`),
+ *               2 = the exploration draws of a tabular policy inside a fused closed-loop rollout
+ *               (bsx_<family>_policy_rollout, epsilon > 0); its key is the caller's explore_seed, not the
+ *               environment's seed, and a (lane, step) triple uses block 0 only: U() — words 0, 1 — and, if
+ *               U < epsilon, RandInt(num_actions) — word 2.  Nothing is drawn by a lane that resets on that
+ *               call, nor when epsilon == 0; streams 0 and 1 never depend on it.
  *   draws consume words in order:
  *     U()        2 words a,b : k = (a>>5)<<26 | (b>>6) ; U = k * 2^-53   (numpy legacy rand())
  *     Bern()     1 word      : word >> 31                                 (binomial(1, .5))
@@ -44,6 +49,7 @@
 
 #define BSX_STREAM_ENV 0u
 #define BSX_STREAM_WRAP 1u
+#define BSX_STREAM_POLICY 2u
 
 typedef struct { uint32_t v[4]; } bsx_u32x4;
 
