@@ -149,7 +149,9 @@ def _build_locked(force, verbose, variants):
     # the slowest files first (sweep_mixed.hip holds every family's body, the physics families the most instantiations)
     slow = ('sweep_mixed', 'cartpole', 'umbrella_chain', 'memory_chain', 'mountain_car', 'deep_sea')
     jobs.sort(key=lambda j: next((i for i, n in enumerate(slow) if os.path.basename(j[0]).startswith(n)), len(slow)))
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(os.cpu_count() or 8, len(jobs))) as ex:
+    # (MAX_JOBS when it is set — a shared machine reports far more cores than a job may use — and never more than 16)
+    workers = min(int(os.environ.get('MAX_JOBS') or os.cpu_count() or 8), 16, len(jobs))
+    with concurrent.futures.ThreadPoolExecutor(max_workers=max(workers, 1)) as ex:
       list(ex.map(lambda j: _compile(j[0], j[1], extra=j[2]), jobs))
   for so_path, objs, hash_path in plans:
     if objs is None:

@@ -6,7 +6,7 @@
 // path of an explicit reset() at its next call.  What the forced branch does BEYOND taking that path is done here:
 // cartpole (classic) and mountain_car keep the running episode's return in the step counter of the word and fold it into
 // the raw_return column only when an episode ends; a forced reset in mid-episode folds the k rewards the abandoned
-// episode has paid (small_obs.h, cartpole_env::core / mountain_car_env::core), and so does the mark.  A word whose bit
+// episode has paid (cartpole_env::core, mountain_car_env::core), and so does the mark.  A word whose bit
 // is already set (after LAST, fresh, marked before) is returned as it is: nothing is folded twice.
 #ifndef BSX_LANE_RESET_H_
 #define BSX_LANE_RESET_H_

@@ -1,8 +1,9 @@
 // cartpole.hip — C-ABI entry points of cartpole / swingup (bsuite/environments/cartpole.py:37-177, bsuite/experiments/cartpole_swingup/cartpole_swingup.py:81-150; auto-reset of bsuite/environments/base.py:54-65).
-// Device code: small_obs.h (cartpole_env).  One translation unit per small-observation family: the families' kernels are independent
+// Device code: cartpole_env.h on the skeleton of small_obs.h.  One translation unit per small-observation family: the families' kernels are independent
 // template instantiations, and compiling them side by side is what keeps a clean build() under a minute (round 6; as ONE
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
+#include "cartpole_env.h"
 
 static int cartpole_make(const bsx_cartpole_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, cartpole_env::args* a) {
   if (cfg == nullptr) return BSX_ENULL;

@@ -9,16 +9,21 @@
 //   observe  bsx_hot_stream_kernel<catch_hot,2,256>: pure store stream over [B x rows*cols] f32.
 //            rows*cols = 50 is not a multiple of 4, so a 16-byte chunk may straddle two lanes'
 //            boards (one division per chunk, spill-over elements patched from lane l+1's state).
-#include "bsx_host.h"
+#include "bsx_pair_host.h"
 #include "catch_fam.h"
 #include "pair_mixed.h"
+
+// The cfg's range check, the same for every entry point.
+static int catch_check_cfg(const bsx_catch_t* cfg) {
+  return (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) ? BSX_ERANGE : 0;
+}
 
 static int catch_make(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
                       bsx_timestep_t out, double* info, catch_fam::args* a) {
   if (cfg == nullptr) return BSX_ENULL;
   int rc = bsx_check_call(call, action, out, /*delta_ok=*/true, /*narrow_ok=*/true);
   if (rc != 0) return rc;
-  if (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) return BSX_ERANGE;
+  if ((rc = catch_check_cfg(cfg)) != 0) return rc;
   if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
   a->ctl = bsx_make_ctl(call);
   a->action = action; a->state = state; a->out = out; a->info = info;
@@ -40,8 +45,8 @@ extern "C" int bsx_catch_step(const bsx_catch_t* cfg, const bsx_call_t* call, co
 extern "C" int bsx_catch_policy_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
                                         int32_t* state, bsx_timestep_t out, double* info) {
   if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  if (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) return BSX_ERANGE;
-  int rc = bsx_check_policy_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), state, out, info);
+  int rc = catch_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_policy_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), state, out, info);
   if (rc != 0 || call->n_lanes == 0) return rc;
   catch_fam::args a;
   // (the action pointer of a policy rollout is never read: actions_out stands in for it in the common checks)
@@ -63,9 +68,7 @@ extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catc
     a.ctl.state_in = call->state_alt;            // pipelined sweeps: the advance reads the other column
     const uint32_t cells = (uint32_t)(cfg->rows * cfg->columns);
     if (cells < 4u) return BSX_ERANGE;
-    bsx_stream_seg<catch_hot> sg;
-    sg.obs = out.observation; sg.state = state; sg.n_lanes = a.ctl.n_lanes; sg.cells = cells;
-    sg.cells_magic = bsx_div_magic(cells); sg.dv = bsx_make_div64(cells); sg.fn = catch_hot{cfg->rows, cfg->columns};
+    const bsx_stream_seg<catch_hot> sg = bsx_make_stream_seg(out.observation, state, a.ctl.n_lanes, cells, catch_hot{cfg->rows, cfg->columns});
     // Whole-sweep group, small boards, one state column (no state_alt): phase 0 — latency-bound, its memory pipe
     // idle — writes the segment's boards itself as fused tiles; the segment leaves the phase-1 store stream, where
     // its 8 KiB runs went at 3.7 TB/s (tools/sweep_stream_parts.py: 27 MB in 7.3 us of a 145 us stream).
@@ -75,7 +78,7 @@ extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catc
     const bool fused = g->family == BSX_FAM_SWEEP_MIXED && call->state_alt == nullptr && cells <= BSX_FUSED_CATCH_MAX_CELLS;
     if (fused) a.tile_cells_magic = sg.cells_magic;
     return bsx_mixed_put(g, BSX_FAM_CATCH, index, call, &a, sizeof(a), &sg, sizeof(sg),
-                              (uint64_t)(a.ctl.n_lanes + BSX_BLOCK - 1) / BSX_BLOCK,
+                              (uint64_t)bsx_blocks_of(a.ctl.n_lanes),
                               fused ? 0 : bsx_flat_blocks((uint64_t)a.ctl.n_lanes * cells, PAIR_CATCH_K), 0);
   }
   rc = bsx_group_check_set(g, BSX_FAM_CATCH, index, call, sizeof(catch_fam::args),

@@ -5,6 +5,7 @@
 #define BSX_CATCH_FAM_H_
 
 #include "bsx_device.h"
+#include "bsx_policy.h"
 
 #define CATCH_RESET_BIT (1 << 24)
 // Bits 25..31 of the packed state: misses not yet folded into the total_regret column (ABI v10).  A miss costs

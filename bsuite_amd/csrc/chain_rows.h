@@ -2,7 +2,8 @@
 #ifndef BSX_CHAIN_ROWS_H_
 #define BSX_CHAIN_ROWS_H_
 
-#include "small_obs.h"
+#include "../../include/bsuite_amd.h"
+#include "bsx_rows.h"
 
 // The row path of a chain segment: the call's scratch, if it brings one and the row is wide.
 template <class Env>

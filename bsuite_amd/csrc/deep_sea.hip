@@ -15,7 +15,7 @@
 // Decoupling the two is what makes the store stream fast: single-kernel variants that advance
 // lanes, synchronise and then store (per-block 230 KB tiles, or flat 16 KiB runs with ping-pong
 // state) measured 5.1-5.5 TB/s against 6.2-6.4 TB/s for this pair (profiles/r01/ab_*.log).
-#include "bsx_host.h"
+#include "bsx_pair_host.h"
 #include "deep_sea_fam.h"
 #include "pair_mixed.h"
 
@@ -89,9 +89,7 @@ __global__ void __launch_bounds__(BSX_BLOCK) deep_sea_step1_kernel(const deep_se
   static_assert(DS_MAP_WORDS <= 2 * BSX_WAVE, "the per-wave copy of the action mapping is two passes at most");
   if (wl < map_words) map.map[wl] = a.mapping_bits[wl];
   if (wl + BSX_WAVE < map_words) map.map[wl + BSX_WAVE] = a.mapping_bits[wl + BSX_WAVE];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  bsx_wave_sync();
 
 
   // The new packed state of lane lane_b + d given its state word w and action; `writer` publishes it.
@@ -141,13 +139,18 @@ __global__ void __launch_bounds__(BSX_BLOCK) deep_sea_step1_kernel(const deep_se
   }
 }
 
+// The cfg's range check, the same for every entry point.
+static int deep_sea_check_cfg(const bsx_deep_sea_t* cfg) {
+  return (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) ? BSX_ERANGE : 0;
+}
+
 // Validates one call's arguments and fills the kernel argument struct (shared by step and group).
 static int deep_sea_make(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action,
                          int32_t* state, bsx_timestep_t out, double* info, deep_sea_fam::args* a) {
   if (cfg == nullptr) return BSX_ENULL;
   int rc = bsx_check_call(call, action, out, /*delta_ok=*/true, /*narrow_ok=*/true);
   if (rc != 0) return rc;
-  if (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) return BSX_ERANGE;
+  if ((rc = deep_sea_check_cfg(cfg)) != 0) return rc;
   if (call->stream.mt_state != nullptr && !cfg->deterministic && call->stream.mt_gauss == nullptr)
     return BSX_ENULL;                      // the stochastic variant draws randn: needs the gauss cache columns
   if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
@@ -192,8 +195,8 @@ extern "C" int bsx_deep_sea_step(const bsx_deep_sea_t* cfg, const bsx_call_t* ca
 extern "C" int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
                                            int32_t* state, bsx_timestep_t out, double* info) {
   if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  if (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) return BSX_ERANGE;
-  int rc = bsx_check_policy_call(call, policy, bsx_policy_states_deep_sea(cfg->size), state, out, info);
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_policy_call(call, policy, bsx_policy_states_deep_sea(cfg->size), state, out, info);
   if (rc != 0 || call->n_lanes == 0) return rc;
   deep_sea_fam::args a;
   // (the action pointer of a policy rollout is never read: actions_out stands in for it in the common checks)
@@ -216,11 +219,9 @@ extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_d
     a.ctl.state_in = call->state_alt;            // pipelined sweeps: the advance reads the other column
     const uint32_t cells = (uint32_t)(cfg->size * cfg->size);
     if (cells < 4u) return BSX_ERANGE;
-    bsx_stream_seg<deep_sea_hot> sg;
-    sg.obs = out.observation; sg.state = state; sg.n_lanes = a.ctl.n_lanes; sg.cells = cells;
-    sg.cells_magic = bsx_div_magic(cells); sg.dv = bsx_make_div64(cells); sg.fn = deep_sea_hot{cfg->size};
+    const bsx_stream_seg<deep_sea_hot> sg = bsx_make_stream_seg(out.observation, state, a.ctl.n_lanes, cells, deep_sea_hot{cfg->size});
     return bsx_mixed_put(g, BSX_FAM_DEEP_SEA, index, call, &a, sizeof(a), &sg, sizeof(sg),
-                              (uint64_t)(a.ctl.n_lanes + BSX_BLOCK - 1) / BSX_BLOCK,
+                              (uint64_t)bsx_blocks_of(a.ctl.n_lanes),
                               bsx_flat_blocks((uint64_t)a.ctl.n_lanes * cells, PAIR_DEEP_SEA_K), 0);
   }
   rc = bsx_group_check_set(g, BSX_FAM_DEEP_SEA, index, call, sizeof(deep_sea_fam::args),

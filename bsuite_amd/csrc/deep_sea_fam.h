@@ -5,6 +5,7 @@
 #define BSX_DEEP_SEA_FAM_H_
 
 #include "bsx_device.h"
+#include "bsx_policy.h"
 
 #define DS_RESET_BIT (1 << 17)
 // Bit 18 of the packed state: the parity of the call index that will READ the word next — every advance writes

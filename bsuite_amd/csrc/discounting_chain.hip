@@ -1,8 +1,9 @@
 // discounting_chain.hip — C-ABI entry points of discounting_chain (bsuite/environments/discounting_chain.py:63-88; auto-reset of bsuite/environments/base.py:54-65).
-// Device code: small_obs.h (discounting_chain_env).  One translation unit per small-observation family: the families' kernels are independent
+// Device code: discounting_chain_env.h on the skeleton of small_obs.h.  One translation unit per small-observation family: the families' kernels are independent
 // template instantiations, and compiling them side by side is what keeps a clean build() under a minute (round 6; as ONE
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
+#include "discounting_chain_env.h"
 
 static int discounting_chain_make(const bsx_discounting_chain_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out, discounting_chain_env::args* a) {
   if (cfg == nullptr) return BSX_ENULL;

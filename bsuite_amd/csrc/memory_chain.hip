@@ -1,8 +1,9 @@
 // memory_chain.hip — C-ABI entry points of memory_chain (bsuite/environments/memory_chain.py:60-97; auto-reset of bsuite/environments/base.py:54-65).
-// Device code: small_obs.h (memory_chain_env).  One translation unit per small-observation family: the families' kernels are independent
+// Device code: memory_chain_env.h on the skeleton of small_obs.h.  One translation unit per small-observation family: the families' kernels are independent
 // template instantiations, and compiling them side by side is what keeps a clean build() under a minute (round 6; as ONE
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
+#include "memory_chain_env.h"
 
 #include "chain_rows.h"
 

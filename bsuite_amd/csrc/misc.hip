@@ -4,6 +4,7 @@
 
 #include "bsx_host.h"
 #include "bsx_lane_reset.h"
+#include "bsx_pair_host.h"
 #include "pair_mixed.h"
 
 extern "C" int bsx_abi_version(void) { return BSX_ABI_VERSION; }
@@ -39,7 +40,7 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_index_decode_kernel(int32_t* __
 
 int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes, int32_t family, int32_t p0, int32_t p1,
                             bool rollout, hipStream_t st) {
-  const int64_t blocks = (n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(n_lanes);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   bsx_index_decode_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(rows, state, n_lanes, family, p0, p1, rollout ? 1 : 0);
   return 0;
@@ -76,7 +77,7 @@ extern "C" int bsx_calib_fill(void* dst, int64_t n_bytes, int32_t nontemporal, v
   if ((reinterpret_cast<uintptr_t>(dst) & 15u) != 0) return BSX_EALIGN;
   if (n_bytes == 0) return 0;
   const int64_t n16 = n_bytes / 16;
-  const int64_t blocks = (n16 + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(n16);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   hipStream_t st = (hipStream_t)hip_stream;
   if (nontemporal) calib_fill_kernel<true><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>((bsx_f4*)dst, n16);
@@ -104,7 +105,7 @@ extern "C" int bsx_calib_copy(void* dst, const void* src, int64_t n_bytes, int32
   if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) != 0) return BSX_EALIGN;
   if (n_bytes == 0) return 0;
   const int64_t n16 = n_bytes / 16;
-  const int64_t blocks = (n16 + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(n16);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   hipStream_t st = (hipStream_t)hip_stream;
   const dim3 g((unsigned)blocks), b(BSX_BLOCK);
@@ -155,7 +156,7 @@ extern "C" int bsx_bsuite_info(int32_t family, int32_t variant, int64_t n_lanes,
   if (info == nullptr || info_out == nullptr) return BSX_ENULL;
   const bool pending = folded && (family == BSX_FAM_CATCH || (family == BSX_FAM_CARTPOLE && variant == 0) || family == BSX_FAM_MOUNTAIN_CAR);
   if (pending && state == nullptr) return BSX_ENULL;
-  const int64_t blocks = (n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(n_lanes);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   bsuite_info_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
       family, variant, n_lanes, state, info, n_info, pending ? 1 : 0, info_out);
@@ -190,7 +191,7 @@ extern "C" int bsx_lane_reset_mark(int32_t family, int32_t variant, int64_t n_la
   if (mask == nullptr || state == nullptr) return BSX_ENULL;
   const int folds = bsx_lane_reset_folds(family, variant, folded);
   if (folds && info == nullptr) return BSX_ENULL;
-  const int64_t blocks = (n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(n_lanes);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   bsx_lane_reset_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
       mask, state, info, n_lanes, family, variant, folds);
@@ -216,7 +217,7 @@ extern "C" int bsx_stream_dump(uint64_t seed, uint64_t lane0, int64_t n_lanes, u
   if (words == nullptr) return BSX_ENULL;
   if (n_lanes < 0 || n_words < 0 || n_words > 1024) return BSX_EINVAL;
   if (n_lanes == 0 || n_words == 0) return 0;
-  const int64_t blocks = (n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(n_lanes);
   stream_dump_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
       seed, lane0, n_lanes, step, (uint32_t)stream_id, n_words, words, normals);
   return bsx_launch_status();

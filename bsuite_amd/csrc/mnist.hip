@@ -86,7 +86,7 @@ extern "C" int bsx_mnist_step(const bsx_mnist_t* cfg, const bsx_call_t* call, co
   if (rc != 0) return rc;
   if (call->n_lanes == 0) return 0;
   hipStream_t st = (hipStream_t)call->hip_stream;
-  const int64_t blocks_a = (call->n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks_a = bsx_blocks_of(call->n_lanes);
   const uint64_t blocks_o = bsx_flat_blocks((uint64_t)call->n_lanes * o.cells, MNIST_K);
   if (blocks_a > 0x7FFFFFFF || blocks_o > 0x7FFFFFFFull) return BSX_EINVAL;
   const int n_steps = bsx_n_steps(call);
@@ -124,7 +124,7 @@ extern "C" int bsx_group_set_mnist(bsx_group_t* g, int32_t index, const bsx_mnis
     if (rc != 0) return rc;
     a.ctl.state_in = call->state_alt;            // pipelined sweeps: the advance reads the other column
     return bsx_mixed_put(g, BSX_FAM_MNIST, index, call, &a, sizeof(a), &o, sizeof(o),
-                              (uint64_t)(call->n_lanes + BSX_BLOCK - 1) / BSX_BLOCK,
+                              (uint64_t)bsx_blocks_of(call->n_lanes),
                               bsx_flat_blocks((uint64_t)call->n_lanes * o.cells, PAIR_MNIST_K), 0);
   }
   rc = bsx_group_check_set(g, BSX_FAM_MNIST, index, call, sizeof(mnist_args), sizeof(mnist_observe_args), 0);
@@ -133,7 +133,7 @@ extern "C" int bsx_group_set_mnist(bsx_group_t* g, int32_t index, const bsx_mnis
   if (rc != 0) return rc;
   memcpy(&g->args[(size_t)index * sizeof(a)], &a, sizeof(a));
   memcpy(&g->args2[(size_t)index * sizeof(o)], &o, sizeof(o));
-  const uint64_t b1 = (uint64_t)(call->n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const uint64_t b1 = (uint64_t)bsx_blocks_of(call->n_lanes);
   const uint64_t b2 = bsx_flat_blocks((uint64_t)call->n_lanes * o.cells, PAIR_MNIST_K);
   if (b1 > 0x3FFFFFFFull || b2 > 0x3FFFFFFFull) return BSX_EINVAL;
   g->blocks[index] = (int32_t)b1; g->blocks2[index] = (int32_t)b2;

@@ -126,9 +126,7 @@ __device__ __forceinline__ void mnist_observe_chunks(const mnist_observe_args& a
       l.x = a.lut[4u * wl]; l.y = a.lut[4u * wl + 1u]; l.z = a.lut[4u * wl + 2u]; l.w = a.lut[4u * wl + 3u];
     }
     reinterpret_cast<bsx_f4*>(s_lut)[wl] = l;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    bsx_wave_sync();
   }
 #pragma unroll
   for (int u = 0; u < K; ++u) {   // four int8 pixels of image idx: one aligned dword of the table (row 0 when nothing shows)

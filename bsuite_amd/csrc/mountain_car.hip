@@ -1,8 +1,9 @@
 // mountain_car.hip — C-ABI entry points of mountain_car (bsuite/environments/mountain_car.py:62-90; auto-reset of bsuite/environments/base.py:54-65).
-// Device code: small_obs.h (mountain_car_env).  One translation unit per small-observation family: the families' kernels are independent
+// Device code: mountain_car_env.h on the skeleton of small_obs.h.  One translation unit per small-observation family: the families' kernels are independent
 // template instantiations, and compiling them side by side is what keeps a clean build() under a minute (round 6; as ONE
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
+#include "mountain_car_env.h"
 
 static int mountain_car_make(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, mountain_car_env::args* a) {
   if (cfg == nullptr) return BSX_ENULL;

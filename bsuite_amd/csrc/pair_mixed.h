@@ -1,11 +1,12 @@
 // pair_mixed.h — host interface of the mixed groups of a heterogeneous sweep:
 //   BSX_FAM_PAIR_MIXED   deep_sea + catch + mnist segments (pair_mixed.hip): one advance launch, one stream launch
 //   BSX_FAM_SWEEP_MIXED  segments of ALL families: phase 0 = every lane of the sweep advanced by ONE launch
-//                        (small_obs.hip, sweep_phase0_kernel), phase 1 = the store stream of pair_mixed.hip
+//                        (sweep_mixed.hip, sweep_phase0_kernel), phase 1 = the store stream of pair_mixed.hip
 #ifndef BSX_PAIR_MIXED_H_
 #define BSX_PAIR_MIXED_H_
 
 #include "bsx_host.h"
+#include "bsx_pair_device.h"
 #include "catch_fam.h"
 #include "deep_sea_fam.h"
 #include "mnist_fam.h"
@@ -17,18 +18,18 @@
 // Records one segment in a BSX_FAM_PAIR_MIXED / BSX_FAM_SWEEP_MIXED group.  `adv`: the segment's phase-0
 // argument struct; `str`: its observation-stream argument struct (NULL for the small-observation families,
 // which have no phase 1); both are copied verbatim into fixed-stride slots of the group's device tables.
-// `lds`: dynamic LDS the segment's phase-0 workgroups need (packed observation records, small_obs.hip).
+// `lds`: dynamic LDS the segment's phase-0 workgroups need (the bit planes of wide rows, small_obs.h).
 int bsx_mixed_put(bsx_group* g, int32_t family, int32_t index, const bsx_call_t* call,
                   const void* adv, size_t adv_size, const void* str, size_t str_size,
                   uint64_t blocks1, uint64_t blocks2, size_t lds);
 
 // launch of the mixed observation stream kernel (pair_mixed.hip) over a group's phase-1 tables
 int bsx_mixed_launch_stream(bsx_group* g, hipStream_t st);
-// phase 0 of a BSX_FAM_SWEEP_MIXED group (small_obs.hip)
+// phase 0 of a BSX_FAM_SWEEP_MIXED group (sweep_mixed.hip)
 int bsx_sweep_launch_phase0(bsx_group* g, hipStream_t st);
 // the split closed-loop step of a whole-sweep group (sweep_mixed.hip)
 int bsx_sweep_launch_split(bsx_group* g, hipStream_t st);
-// one launch: the phase-1 store stream of `streams_of` beside phase 0 of `advances_of` (small_obs.hip)
+// one launch: the phase-1 store stream of `streams_of` beside phase 0 of `advances_of` (sweep_mixed.hip)
 int bsx_sweep_launch_pipelined(bsx_group* streams_of, bsx_group* advances_of, hipStream_t st);
 
 // One workgroup of the mixed observation store stream: `block` of the phase-1 grid runs its segment's

@@ -64,7 +64,7 @@ static int pair_mixed_launch(bsx_group* g, int phase, hipStream_t st) {
 }
 
 // BSX_FAM_SWEEP_MIXED: phase 0 advances every lane of every family (and bumps the shared call counter
-// itself, see small_obs.hip), phase 1 is the same store stream.
+// itself, see sweep_mixed.hip), phase 1 is the same store stream.
 static int sweep_mixed_launch(bsx_group* g, int phase, hipStream_t st) {
   int rc = 0;
   if (phase != 1) rc = bsx_sweep_launch_phase0(g, st);

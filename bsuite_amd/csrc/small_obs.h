@@ -1,12 +1,41 @@
-// small_obs.h — device code of the families whose observation is a short row (1..256 floats per lane):
-//   bandit            bsuite/environments/bandit.py:54-64
-//   memory_chain      bsuite/environments/memory_chain.py:60-97
-//   umbrella_chain    bsuite/environments/umbrella_chain.py:60-92
-//   discounting_chain bsuite/environments/discounting_chain.py:63-88
-//   cartpole/swingup  bsuite/environments/cartpole.py:37-177,
-//                     bsuite/experiments/cartpole_swingup/cartpole_swingup.py:81-150
-//   mountain_car      bsuite/environments/mountain_car.py:62-90
+// small_obs.h — the kernel skeleton of the families whose observation is a short row (1..256 floats per lane).  The
+// families themselves are one header each:
+//   bandit_env.h             bsuite/environments/bandit.py:54-64
+//   memory_chain_env.h       bsuite/environments/memory_chain.py:60-97
+//   umbrella_chain_env.h     bsuite/environments/umbrella_chain.py:60-92
+//   discounting_chain_env.h  bsuite/environments/discounting_chain.py:63-88
+//   cartpole_env.h           bsuite/environments/cartpole.py:37-177,
+//                            bsuite/experiments/cartpole_swingup/cartpole_swingup.py:81-150
+//   mountain_car_env.h       bsuite/environments/mountain_car.py:62-90
 // each with the auto-reset of bsuite/environments/base.py:54-65.
+//
+// What a family `Env` provides to the skeleton (everything static):
+//   ALWAYS
+//     HAS_REGS, PACKED          which of the two groups below apply
+//     struct args               the kernel argument: bsx_ctl ctl, const int32_t* action, bsx_timestep_t out, int32_t obs_numel,
+//                               then the family's columns and parameters
+//     step<LOG, MT>(a, i, oi, lane, step, o, reward) -> step type
+//                               one reset() / step() of lane i against its columns in memory: reads action[oi], writes the
+//                               row into o[] (<= 8 floats) and the f64 reward; PACKED: step<LOG, MT, true>(..., &sink) leaves
+//                               HEAD floats in o[] and the rest of the row as bits in the sink
+//   HAS_REGS — the lane's state fits in registers: fused rollouts (small_obs_regs_rollout) and the lean eager step with
+//   several lanes per thread (small_obs_eager2_kernel) hold it there; small_regs_defaults has the no-op members
+//     struct regs; clear(r); load(a, i, r); store(a, i, r)          the state, zeroed / from / to its columns
+//     reset_pending(r)          does the lane begin an episode at its next step?
+//     core<LOG, MT, IREGS, TAB, POOL, V, NOFORCE>(a, r, act, i, lane, step, o, reward, s_tab, s_pool) -> step type
+//                               step() on the registers: the same transitions, draws and info updates
+//     load_info<V> / store_info<V>(a, i, r)                          the bsuite_info columns that core<IREGS = true> keeps in r
+//     N_VARIANTS, numel_of(v), variant_of(a)                         compile-time variants of the lean rollout (row length), -1 = none fits
+//     TABLE_MAX_BYTES, table_fits(a), table_bytes(a), stage_tables(a, s_dyn)   a table the rollout stages in LDS (0 = none)
+//     POOLED_RESETS, wants_reset<NOFORCE>(a, r), reset_part(a, lane, step, part, owner, pool)
+//                               big launches: a lane's reset draws computed by the workgroup's pool, two parts per lane
+//     ROWS_VIA_LDS              big launches: a wave's rows leave as 16-byte chunks through LDS (small_obs_store_rows_wave)
+//     EAGER_LPT_MIN_BLOCKS, EAGER_LPT                                lean eager step: lanes per thread, and from how many workgroups up
+//   PACKED — the row length is a parameter and the row is HEAD floats followed by values that one or two bits encode
+//     rows_t                    the row format of row_stream.h (memory_rows, umbrella_rows); HEAD, PLANES from it
+//     decode(bit0, bit1)        the float that a tile element's plane bits stand for
+//     tf_table_fits(a)          do the time fractions 1 - t / L fit the tile's LDS table?
+//     args: L, numel_magic (bsx_div_magic(obs_numel)), rows, row_plane_words (the call's row scratch: chain_rows.h)
 //
 // One kernel shape for all of them: thread t advances lane (block*256 + t) from coalesced SoA column
 // loads and either stores its short observation row itself or — the wide rows of memory_chain /
@@ -17,13 +46,7 @@
 #ifndef BSX_SMALL_OBS_H_
 #define BSX_SMALL_OBS_H_
 
-#include <type_traits>
-
 #include "bsx_host.h"
-#include "bsx_math.h"
-#include "catch_fam.h"
-#include "deep_sea_fam.h"
-#include "mnist_fam.h"
 #include "pair_mixed.h"
 #include "row_stream.h"
 
@@ -95,7 +118,7 @@ struct bsx_reset_pool {
 // faster everywhere (ab_eager_output_policy.log).  NEITHER for rows written as 8-byte pieces at the row stride (cartpole
 // row-per-lane: 18 -> 25 us non-temporal — partial lines want the L2 to merge them).  deep_sea / catch / mnist / the sweep are
 // not touched by this (ab_small_nt_other_paths.log).  The policy of each kind of output, in a fused rollout and in an eager step:
-// (struct bsx_out_policy, bsx_policy, BSX_OUT_SCALARS — the reward / discount / step_type columns — and BSX_OUT_INDEX: bsx_device.h)
+// (struct bsx_out_policy, bsx_policy, BSX_OUT_SCALARS — the reward / discount / step_type columns: bsx_device.h; BSX_OUT_INDEX: bsx_pair_device.h)
 constexpr bsx_out_policy BSX_OUT_ROW12 = {BSX_ST_NT, BSX_ST_WT};          // rows of one or two floats stored by their own thread
 constexpr bsx_out_policy BSX_OUT_STAGED = {BSX_ST_NT, BSX_ST_WT};         // rows staged through a wave's LDS, stored as 16-byte chunks
 constexpr bsx_out_policy BSX_OUT_PARTIAL = {BSX_ST_PLAIN, BSX_ST_PLAIN};  // rows of 4 / 6 / 8 floats stored by their own thread as
@@ -180,9 +203,7 @@ __device__ __forceinline__ void small_obs_store_rows_wave(Chunk chunk, const flo
     for (int k = 0; k < 7; ++k)
       if (k < numel) mine[k] = o[k];
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  bsx_wave_sync();
   const int chunks = 16 * numel;                                 // 64 rows x numel floats / 4
   for (int c = wl; c < chunks; c += 64)
     bsx_st<bsx_policy(BSX_OUT_STAGED, ROLLOUT_ST)>(chunk(c), reinterpret_cast<const bsx_f4*>(s_wave)[c]);
@@ -408,6 +429,8 @@ __device__ __forceinline__ void small_obs_regs_rollout(const typename Env::args&
     Env::store(a, i, rg);
     if constexpr (IREGS) Env::template store_info<V>(a, i, rg);
   }
+  // (bsx_pool_counts written out: through the helper, the assembly listings of cartpole, memory_chain and mountain_car
+  // are no longer the same text — profiles/layout_split/README.md)
   if (a.ctl.counters != nullptr) {
     if (n_last) atomicAdd(&s_cnt[0], n_last);
     if (n_first) atomicAdd(&s_cnt[1], n_first);
@@ -473,9 +496,7 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
       const uint32_t wstride = 2u * (uint32_t)numel;                       // words per plane of one wave
       uint32_t* __restrict__ wplanes = reinterpret_cast<uint32_t*>(s_obs) + (threadIdx.x >> 6) * ((uint32_t)R::PLANES * wstride);
       for (uint32_t w = (uint32_t)wl; w < (uint32_t)R::PLANES * wstride; w += BSX_WAVE) wplanes[w] = 0u;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      bsx_wave_sync();
       if (mine) {
         double reward = 0.0;
         float o[Env::HEAD];
@@ -498,9 +519,7 @@ __device__ __forceinline__ void small_obs_body(const typename Env::args& a, cons
         }
       }
       bsx_count_types(a.ctl, type, s_cnt);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      bsx_wave_sync();
       const int64_t wave_lane0 = lane0 + (int64_t)(threadIdx.x & ~63u);
       if (wave_lane0 < B) {                                              // (uniform per wave)
         uint32_t* __restrict__ gp = a.rows + (uint64_t)(wave_lane0 >> 6) * wstride;
@@ -819,7 +838,7 @@ static int small_obs_group_put(bsx_group* g, int32_t family, int32_t index, cons
                                const typename Env::args& a_in) {
   static_assert(sizeof(typename Env::args) <= SMALL_MIXED_STRIDE, "argument struct exceeds the mixed-group slot");
   typename Env::args a = a_in;
-  const uint64_t nb = (uint64_t)(a.ctl.n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const uint64_t nb = (uint64_t)bsx_blocks_of(a.ctl.n_lanes);
   if (g != nullptr && g->family == BSX_FAM_SWEEP_MIXED) {     // one segment of the whole-sweep group
     if (small_obs_rows<Env>(a)) {
       // wide rows with a row scratch: phase 0 leaves them packed, the phase-1 store stream writes the observations
@@ -923,10 +942,10 @@ static int launch_small_obs(const typename Env::args& a, int n_steps, void* hip_
     if (Env::PACKED && !bsx_small_direct_shape(a.obs_numel)) regs_v = -1;      // wide rows: the LDS bit planes, step by step
     static const int eager2_min_blocks = bsx_env_int("BSX_EAGER2_MIN_BLOCKS", Env::EAGER_LPT_MIN_BLOCKS);
     static const int eager_lpt_knob = bsx_env_int("BSX_EAGER_LPT", Env::EAGER_LPT);
-    eager2 = eager2_min_blocks > 0 && Env_variant >= 0 && (a.ctl.n_lanes + BSX_BLOCK - 1) / BSX_BLOCK >= eager2_min_blocks;
+    eager2 = eager2_min_blocks > 0 && Env_variant >= 0 && bsx_blocks_of(a.ctl.n_lanes) >= eager2_min_blocks;
     eager_lpt = eager_lpt_knob;
   }
-  const int64_t blocks = (a.ctl.n_lanes + BSX_BLOCK - 1) / BSX_BLOCK;
+  const int64_t blocks = bsx_blocks_of(a.ctl.n_lanes);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   const size_t lds = n_steps > 1 ? small_obs_rollout_lds<Env>(a) : small_obs_lds<Env>(a);
   const dim3 g((unsigned)blocks), b(BSX_BLOCK);
@@ -984,74 +1003,21 @@ static int launch_small_obs(const typename Env::args& a, int n_steps, void* hip_
   return bsx_launch_status();
 }
 
-// ------------------------------------------------------------------------------ bandit
-// A family with a one-word state and no table, register-resident in a fused rollout (small_obs_regs_rollout): what the
-// interface needs beyond regs / load / store / core.
+// ------------------------------------------------------------------------------ shared by more than one family
+// What a register-resident family (HAS_REGS) inherits unless it has something to say: no pooled resets, rows stored by
+// their own threads, one variant, no table, no info columns held in registers (A = the family's args, R = its regs).  A
+// family that overrides a member declares its own; cartpole, which would override nearly all, declares every member itself.
 struct small_regs_defaults {
   static constexpr bool POOLED_RESETS = false, ROWS_VIA_LDS = false;
   static constexpr int N_VARIANTS = 1, TABLE_MAX_BYTES = 0;
   static constexpr int EAGER_LPT_MIN_BLOCKS = 2048, EAGER_LPT = 2;   // lean eager step: lanes per thread (launch_small_obs)
-  __device__ static __forceinline__ void reset_part(const void*, uint64_t, uint64_t, int, unsigned, bsx_reset_pool*) {}
-};
-
-struct bandit_env : small_regs_defaults {
-  // (register-resident in a fused rollout: the generic loop re-read the reset flag from L2 behind a drain of the previous
-  // step's stores and read-modify-wrote the f64 regret column on every second step — 16 of the step's 33 bytes)
-  static constexpr bool HAS_REGS = true, PACKED = false;
-  __host__ __device__ static constexpr int numel_of(int) { return 1; }
-  struct regs { int32_t st; double inf0; };                    // inf0: total_regret in a fused rollout
-  struct args {
-    bsx_ctl ctl; const int32_t* action; int32_t* state; bsx_timestep_t out; double* info;
-    int32_t obs_numel; int32_t num_actions; double rewards[BSX_BANDIT_MAX_ACTIONS];
-  };
-  static int variant_of(const args&) { return 0; }
-  template <bool NOFORCE = false>
-  __device__ static __forceinline__ bool wants_reset(const args&, const regs&) { return false; }
-  __device__ static __forceinline__ void clear(regs& r) { r.st = 0; }
-  __device__ static __forceinline__ bool reset_pending(const regs& r) { return r.st != 0; }
-  __device__ static __forceinline__ void reset_part(const args&, uint64_t, uint64_t, int, unsigned, bsx_reset_pool*) {}
-  __host__ __device__ static bool table_fits(const args&) { return false; }
-  static size_t table_bytes(const args&) { return 0; }
-  __device__ static __forceinline__ bsx_lds_table stage_tables(const args&, float*) { return (bsx_lds_table)0; }
-  template <int V = -1>
-  __device__ static __forceinline__ void load_info(const args& a, int64_t i, regs& r) { r.inf0 = a.info[i]; }
-  template <int V = -1>
-  __device__ static __forceinline__ void store_info(const args& a, int64_t i, const regs& r) { a.info[i] = r.inf0; }
-  __device__ static __forceinline__ void load(const args& a, int64_t i, regs& r) { r.st = a.state[i]; }
-  __device__ static __forceinline__ void store(const args& a, int64_t i, const regs& r) { a.state[i] = r.st; }
-  // (the same transitions as step() below; tests/test_gpu_rollout.py holds rollout(T) to T step() calls bit for bit)
-  template <int LOG, int MT, bool IREGS = false, bool TAB = false, bool POOL = false, int V = -1, bool NOFORCE = false>
-  __device__ static __forceinline__ int core(const args& a, regs& rg, int act, int64_t i, uint64_t, uint64_t,
-                                             float* o, double& reward, bsx_lds_table = (bsx_lds_table)0,
-                                             const bsx_reset_pool* = nullptr) {
-    BSX_NO_CONTRACT
-    o[0] = 1.0f;                                                // bandit.py:54 (ones)
-    if ((!NOFORCE && a.ctl.force_reset) || rg.st) { rg.st = 0; return BSX_FIRST; }
-    if (act < 0 || act >= a.num_actions) {                      // reference: IndexError (bandit.py:61)
-      bsx_note_invalid_action(a.ctl, i);
-      act = act < 0 ? 0 : a.num_actions - 1;
-    }
-    reward = a.rewards[act];                                    // :61
-    if constexpr (IREGS) rg.inf0 += 1.0 - reward; else a.info[i] += 1.0 - reward;   // :62
-    rg.st = 1;
-    return BSX_LAST;                                            // :64
-  }
-  template <int LOG, int MT>
-  __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t, uint64_t step, float* o, double& reward) {
-    BSX_NO_CONTRACT
-    o[0] = 1.0f;                                                // bandit.py:54 (ones)
-    if (a.ctl.force_reset || a.state[i]) { a.state[i] = 0; return BSX_FIRST; }
-    int act = bsx_action(a.ctl, a.action, oi, step);
-    if (act < 0 || act >= a.num_actions) {                      // reference: IndexError (bandit.py:61)
-      bsx_note_invalid_action(a.ctl, i);
-      act = act < 0 ? 0 : a.num_actions - 1;                    // never read OOB
-    }
-    reward = a.rewards[act];                                    // :61
-    a.info[i] += 1.0 - reward;                                  // :62 (every second call of every lane: a plain
-                                                                //      read-modify-write beats 2^20 atomics, 9.6 vs 11.2 us)
-    a.state[i] = 1;
-    return BSX_LAST;                                            // :64
-  }
+  template <bool NOFORCE = false, class A, class R> __device__ static __forceinline__ bool wants_reset(const A&, const R&) { return false; }
+  template <class A> __device__ static __forceinline__ void reset_part(const A&, uint64_t, uint64_t, int, unsigned, bsx_reset_pool*) {}
+  template <class A> __host__ __device__ static bool table_fits(const A&) { return false; }
+  template <class A> static size_t table_bytes(const A&) { return 0; }
+  template <class A> __device__ static __forceinline__ bsx_lds_table stage_tables(const A&, float*) { return (bsx_lds_table)0; }
+  template <int V = -1, class A, class R> __device__ static __forceinline__ void load_info(const A&, int64_t, R&) {}
+  template <int V = -1, class A, class R> __device__ static __forceinline__ void store_info(const A&, int64_t, const R&) {}
 };
 
 // The time fraction 1 - t / L of the chains' rows (memory_chain.py:64, umbrella_chain.py:64): from the workgroup's LDS
@@ -1066,657 +1032,7 @@ __device__ __forceinline__ float bsx_chain_time_fraction(int t, int L, const Sin
   return (float)(1.0 - (double)t / (double)L);
 }
 
-// ------------------------------------------------------------------------------ memory_chain
-#define MC_RESET_BIT (1 << 28)
-struct memory_chain_env {
-  // Register-resident in a fused rollout of SHORT rows (num_bits <= 6: the row is stored by the lane's own thread) — every
-  // memory_len id has one context bit.  The generic rollout re-read the lane's state word and context from L2 on every
-  // step behind a drain of the previous step's stores (three dependent round trips per step): memory_len/10 took 13.6 us
-  // per step inside rollout(16) against 12.3 us for an eager step() (profiles/r05/bench_default_call1.json).
-  static constexpr bool HAS_REGS = true, PACKED = true, POOLED_RESETS = false, ROWS_VIA_LDS = false;
-  static constexpr int EAGER_LPT_MIN_BLOCKS = 2048, EAGER_LPT = 2;
-  static constexpr int N_VARIANTS = 1;
-  __host__ __device__ static constexpr int numel_of(int) { return 3; }     // variant 0: one context bit, rows of 3 floats
-  struct regs { int32_t st; uint64_t ctx; double inf[2]; };                // inf: total_perfect, total_regret in a fused rollout
-  struct args {
-    bsx_ctl ctl; const int32_t* action; int32_t* state; uint64_t* context; bsx_timestep_t out;
-    double* info; int32_t obs_numel; int32_t L; int32_t nb; uint32_t numel_magic;
-    uint32_t* rows; int64_t row_plane_words;                   // bsx_call_t.row_scratch (bsx_rows.h) + words per plane, or nullptr
-  };
-  // Packed rows: HEAD = [time, query]; element 2+b is 0 unless t == 0, then +-1 by context bit b: plane 0 says
-  // "non-zero", plane 1 carries the context bit (memory_rows, row_stream.h).
-  // (PACKED path: the time fractions in LDS when the chain has at most 1024 steps)
-  __host__ __device__ static bool tf_table_fits(const args& a) { return a.L <= 1023; }
-  typedef memory_rows rows_t;
-  static constexpr int HEAD = rows_t::HEAD, PLANES = rows_t::PLANES;
-  __device__ static float decode(uint32_t nonzero, uint32_t bit) { return rows_t::decode(nonzero, bit); }
-  template <bool PACK, class Sink>
-  __device__ static void observe(const args& a, float* o, int t, int query, uint64_t ctx, const Sink* sink) {
-    BSX_NO_CONTRACT
-    // (PACK: o[0], the time fraction of :64, is step()'s — bsx_chain_time_fraction)
-    if constexpr (!PACK) o[0] = (float)(1.0 - (double)t / (double)a.L);   // memory_chain.py:64
-    o[1] = (t == a.L - 1) ? (float)query : 0.0f;                // :66-67
-    if constexpr (PACK) {
-      if (t == 0) {                                             // :69-70 (the tile is zero-filled before every step)
-        const int n0 = a.nb < 32 ? a.nb : 32;
-        sink->put(0, 0, 0xFFFFFFFFu, n0);
-        sink->put(1, 0, (uint32_t)ctx, n0);
-        if (a.nb > 32) {
-          sink->put(0, 1, 0xFFFFFFFFu, a.nb - 32);
-          sink->put(1, 1, (uint32_t)(ctx >> 32), a.nb - 32);
-        }
-      }
-    } else {
-      for (int b = 0; b < a.nb; ++b)                            // :69-70
-        o[2 + b] = (t == 0) ? (float)(2 * (int)((ctx >> b) & 1ull) - 1) : 0.0f;
-    }
-  }
-  // ---- the register-resident form (small_obs_regs_rollout): state word + context in registers for the T steps
-  static int variant_of(const args& a) { return a.nb == 1 ? 0 : -1; }
-  template <bool NOFORCE = false>
-  __device__ static __forceinline__ bool wants_reset(const args&, const regs&) { return false; }
-  __device__ static __forceinline__ void clear(regs& r) { r.st = 0; r.ctx = 0ull; }
-  __device__ static __forceinline__ bool reset_pending(const regs& r) { return (r.st & MC_RESET_BIT) != 0; }
-  __device__ static __forceinline__ void reset_part(const args&, uint64_t, uint64_t, int, unsigned, bsx_reset_pool*) {}
-  // the time fraction 1 - t / L (an f64 division per step) from a table in LDS that the workgroup fills once per launch with
-  // that same division
-  static constexpr int TABLE_MAX_BYTES = 16384;
-  __host__ __device__ static bool table_fits(const args& a) { return ((int64_t)a.L + 1) * 4 <= TABLE_MAX_BYTES; }
-  static size_t table_bytes(const args& a) { return table_fits(a) ? ((size_t)a.L + 1) * 4 : 0; }
-  __device__ static __forceinline__ bsx_lds_table stage_tables(const args& a, float* s_dyn) {
-    BSX_NO_CONTRACT
-    for (int k = threadIdx.x; k <= a.L; k += BSX_BLOCK) s_dyn[k] = (float)(1.0 - (double)k / (double)a.L);
-    return (bsx_lds_table)s_dyn;
-  }
-  template <int V = -1>
-  __device__ static __forceinline__ void load_info(const args& a, int64_t i, regs& r) { r.inf[0] = a.info[i]; r.inf[1] = a.info[a.ctl.n_lanes + i]; }
-  template <int V = -1>
-  __device__ static __forceinline__ void store_info(const args& a, int64_t i, const regs& r) { a.info[i] = r.inf[0]; a.info[a.ctl.n_lanes + i] = r.inf[1]; }
-  __device__ static __forceinline__ void load(const args& a, int64_t i, regs& r) { r.st = a.state[i]; r.ctx = a.context[i]; }
-  __device__ static __forceinline__ void store(const args& a, int64_t i, const regs& r) { a.state[i] = r.st; a.context[i] = r.ctx; }
-  // One reset()/step() of the lane in `rg` (memory_chain.py:60-97; the same transitions, draws and info updates as step()
-  // below — tests/test_gpu_rollout.py holds rollout(T) to T step() calls bit for bit).  Short rows only: o[0 .. nb + 2).
-  template <int LOG, int MT, bool IREGS = false, bool TAB = false, bool POOL = false, int V = -1, bool NOFORCE = false>
-  __device__ static __forceinline__ int core(const args& a, regs& rg, const int act, int64_t i, uint64_t lane, uint64_t step,
-                                             float* o, double& reward, bsx_lds_table s_tf = (bsx_lds_table)0,
-                                             const bsx_reset_pool* = nullptr) {
-    BSX_NO_CONTRACT
-    const int nb = V == 0 ? 1 : a.nb;
-    const int32_t st = rg.st;
-    int t = st & 0xFFFFF, query = (st >> 20) & 0xFF;
-    uint64_t ctx = rg.ctx;
-    const bool reset = (!NOFORCE && a.ctl.force_reset) || (st & MC_RESET_BIT);
-    if (reset) {                                                // :91-97
-      bsx_draws d;
-      bsx_draws_begin<MT>(&d, a.ctl, i, lane, step);
-      ctx = 0;
-      if (MT == 0 || d.mt == nullptr) {
-        ctx = (uint64_t)bsx_word(&d) & ((1ull << nb) - 1ull);   // BernVec(nb), nb <= 6 here: the low bits of one word
-      } else {
-        uint32_t w = 0;
-        for (int b = 0; b < nb; ++b) ctx |= (uint64_t)bsx_bern_vec_bit(&d, b, &w) << b;
-      }
-      query = (int)bsx_randint(&d, (uint32_t)nb);
-      bsx_draws_end<MT>(&d, a.ctl, i);
-      t = 0;
-      rg.ctx = ctx;
-    }
-    // the observation of the state BEFORE the step's increment (:74; after a reset: of the fresh state)
-    if constexpr (TAB) o[0] = s_tf[t];                          // (t <= L)
-    else o[0] = (float)(1.0 - (double)t / (double)a.L);         // :64
-    o[1] = (t == a.L - 1) ? (float)query : 0.0f;                // :66-67
-#pragma unroll
-    for (int b = 0; b < 6; ++b)
-      if (b < nb) o[2 + b] = (t == 0) ? (float)(2 * (int)((ctx >> b) & 1ull) - 1) : 0.0f;   // :69-70
-    if (reset) { rg.st = t | (query << 20); return BSX_FIRST; }
-    t += 1;                                                     // :75
-    if (t - 1 < a.L) { rg.st = t | (query << 20); return BSX_MID; }   // :77-79
-    const bool hit = act == (int)((ctx >> query) & 1ull);
-    reward = hit ? 1.0 : -1.0;                                  // :83-88
-    if constexpr (IREGS) {
-      if (hit) rg.inf[0] += 1.0; else rg.inf[1] += 2.0;
-    } else {
-      const bool quiet = a.L >= 8 && bsx_info_quiet<LOG>(a.ctl);
-      if (hit) bsx_info_add(quiet, &a.info[i], 1.0); else bsx_info_add(quiet, &a.info[a.ctl.n_lanes + i], 2.0);
-    }
-    rg.st = t | (query << 20) | MC_RESET_BIT;
-    return BSX_LAST;
-  }
-  template <int LOG, int MT, bool PACK = false, class Sink = bsx_bit_sink>
-  __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t lane, uint64_t step, float* o, double& reward,
-                             const Sink* sink = nullptr) {
-    int32_t st = a.state[i];
-    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, oi, step);   // (see umbrella_chain_env::step)
-    int t = st & 0xFFFFF, query = (st >> 20) & 0xFF;
-    uint64_t ctx = a.context[i];
-    const bool resets = a.ctl.force_reset || (st & MC_RESET_BIT);
-    // :64 — of the state BEFORE the increment (:74), or of the fresh one (short rows: observe() does it, where it always was)
-    if constexpr (PACK) o[0] = bsx_chain_time_fraction<PACK>(resets ? 0 : t, a.L, sink);
-    if (resets) {                                               // :91-97
-      bsx_draws d;
-      bsx_draws_begin<MT>(&d, a.ctl, i, lane, step);
-      ctx = 0;
-      if (MT == 0 || d.mt == nullptr) {                         // BernVec(nb) = the low nb bits of ceil(nb/32) words
-        ctx = (uint64_t)bsx_word(&d);
-        if (a.nb > 32) ctx |= (uint64_t)bsx_word(&d) << 32;
-        ctx &= (1ull << a.nb) - 1ull;                           // nb <= 62
-      } else {
-        uint32_t w = 0;
-        for (int b = 0; b < a.nb; ++b) ctx |= (uint64_t)bsx_bern_vec_bit(&d, b, &w) << b;   // one legacy double per bit
-      }
-      query = (int)bsx_randint(&d, (uint32_t)a.nb);
-      bsx_draws_end<MT>(&d, a.ctl, i);
-      t = 0;
-      a.context[i] = ctx;
-      a.state[i] = t | (query << 20);
-      observe<PACK>(a, o, t, query, ctx, sink);
-      return BSX_FIRST;
-    }
-    observe<PACK>(a, o, t, query, ctx, sink);                   // :74 — before the increment
-    t += 1;                                                     // :75
-    if (t - 1 < a.L) { a.state[i] = t | (query << 20); return BSX_MID; }   // :77-79
-    // (the episode's one bsuite_info update: a no-return atomic when episodes are long, i.e. when only a few lanes of a
-    // wave end on a given call — bsx_info_add)
-    const bool quiet = a.L >= 8 && bsx_info_quiet<LOG>(a.ctl);
-    if (act == (int)((ctx >> query) & 1ull)) { reward = 1.0; bsx_info_add(quiet, &a.info[i], 1.0); }   // :83-85
-    else { reward = -1.0; bsx_info_add(quiet, &a.info[a.ctl.n_lanes + i], 2.0); }   // :86-88
-    a.state[i] = t | (query << 20) | MC_RESET_BIT;
-    return BSX_LAST;
-  }
-};
-
-// ------------------------------------------------------------------------------ umbrella_chain
-#define UC_RESET_BIT (1 << 22)
-struct umbrella_chain_env {
-  static constexpr bool HAS_REGS = false, PACKED = true;
-  struct regs { int unused; };
-  struct args {
-    bsx_ctl ctl; const int32_t* action; int32_t* state; bsx_timestep_t out; double* info;
-    int32_t obs_numel; int32_t L; int32_t nd; uint32_t numel_magic;
-    uint32_t* rows; int64_t row_plane_words;                   // bsx_call_t.row_scratch (bsx_rows.h) + words per plane, or nullptr
-  };
-  // Packed rows: HEAD = [need, has, time]; element 3+b is distractor bit b as 0.0 / 1.0 (one plane; umbrella_rows).
-  __host__ __device__ static bool tf_table_fits(const args& a) { return a.L <= 1023; }
-  typedef umbrella_rows rows_t;
-  static constexpr int HEAD = rows_t::HEAD, PLANES = rows_t::PLANES;
-  __device__ static float decode(uint32_t bit, uint32_t) { return rows_t::decode(bit, 0u); }
-  template <bool PACK, int MT, class Sink>
-  __device__ static void observe(const args& a, float* o, int t, int need, int has, bsx_draws* d, const Sink* sink) {
-    BSX_NO_CONTRACT
-    o[0] = (float)need;                                         // umbrella_chain.py:62
-    o[1] = (float)has;                                          // :63
-    // (o[2], the time fraction of :64, is step()'s: bsx_chain_time_fraction)
-    uint32_t w = 0;
-    if constexpr (PACK) {
-      if (MT == 0 || d->mt == nullptr) {
-        // :65 BernVec(nd) IS a run of stream words (bit i of the vector = bit i%32 of word i/32): hand the words to
-        // the tile as they come — a bit-by-bit loop cost ~30 scalar + ~5 vector instructions per distractor
-        // (3400 SALU per wave at nd = 100, profiles/r03/umbrella_distract_before_pmc_sq.json)
-        for (int k = 0; 32 * k < a.nd; ++k) {
-          const int n = a.nd - 32 * k;
-          sink->put(0, k, bsx_word(d), n < 32 ? n : 32);
-        }
-      } else {
-        uint32_t acc = 0;
-        for (int b = 0; b < a.nd; ++b) {                        // MT19937-exact mode: one legacy double per bit
-          acc |= bsx_bern_vec_bit(d, b, &w) << (b & 31);
-          if ((b & 31) == 31 || b == a.nd - 1) { sink->put(0, b >> 5, acc, (b & 31) + 1); acc = 0; }
-        }
-      }
-    } else {
-      for (int b = 0; b < a.nd; ++b) o[3 + b] = (float)bsx_bern_vec_bit(d, b, &w);   // :65 BernVec(nd)
-    }
-  }
-  template <int LOG, int MT, bool PACK = false, class Sink = bsx_bit_sink>
-  __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t lane, uint64_t step, float* o, double& reward,
-                             const Sink* sink = nullptr) {
-    BSX_NO_CONTRACT
-    int32_t st = a.state[i];
-    // (the action matters on the episode's first step only, but which lanes are there is known when the state word has
-    // arrived: loaded now, beside it, not in a second dependent round trip — in any real batch every wave holds such a
-    // lane, and the line is fetched for it anyway)
-    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, oi, step);
-    int t = st & 0xFFFFF, need = (st >> 20) & 1, has = (st >> 21) & 1;
-    bsx_draws d;
-    bsx_draws_begin<MT>(&d, a.ctl, i, lane, step);
-    // (every path below draws from block 0 of the lane's stream: computed once, before the lanes of a wave — at different
-    // episode phases in any real batch — part ways; 659 -> see profiles/r05/ab_umbrella_shared_philox_block.log)
-    bsx_draws_prime(&d);
-    const bool resets = a.ctl.force_reset || (st & UC_RESET_BIT);
-    o[2] = bsx_chain_time_fraction<PACK>(resets ? 0 : t + 1, a.L, sink);   // :64 — of the state AFTER the increment (:69)
-    if (resets) {                                               // :87-92
-      t = 0;
-      need = (int)bsx_bern(&d);
-      has = (int)bsx_bern(&d);
-      observe<PACK, MT>(a, o, t, need, has, &d, sink);
-      bsx_draws_end<MT>(&d, a.ctl, i);
-      a.state[i] = t | (need << 20) | (has << 21);
-      return BSX_FIRST;
-    }
-    t += 1;                                                     // :69
-    if (t == 1) has = (act == 1);   // :71-72 (action_spec: {0,1})
-    int type;
-    if (t == a.L) {                                             // :74-81
-      if (has == need) reward = 1.0;
-      else { reward = -1.0; a.info[i] += 2.0; }
-      observe<PACK, MT>(a, o, t, need, has, &d, sink);
-      type = BSX_LAST;
-    } else {                                                    // :83-85
-      reward = 2.0 * (double)bsx_bern(&d) - 1.0;
-      observe<PACK, MT>(a, o, t, need, has, &d, sink);
-      type = BSX_MID;
-    }
-    bsx_draws_end<MT>(&d, a.ctl, i);
-    a.state[i] = t | (need << 20) | (has << 21) | (type == BSX_LAST ? UC_RESET_BIT : 0);
-    return type;
-  }
-};
-
-// ------------------------------------------------------------------------------ discounting_chain
-#define DC_RESET_BIT (1 << 12)
-struct discounting_chain_env : small_regs_defaults {
-  static constexpr bool HAS_REGS = true, PACKED = false;        // (register-resident in a fused rollout, like the bandit)
-  static constexpr int EAGER_LPT_MIN_BLOCKS = 4096;              // (two lanes per thread: equal at 2^19 lanes)
-  __host__ __device__ static constexpr int numel_of(int) { return 2; }
-  struct regs { int32_t st; };
-  struct args {
-    bsx_ctl ctl; const int32_t* action; int32_t* state; bsx_timestep_t out;
-    int32_t obs_numel; int32_t bonus;
-  };
-  static int variant_of(const args&) { return 0; }
-  template <bool NOFORCE = false>
-  __device__ static __forceinline__ bool wants_reset(const args&, const regs&) { return false; }
-  // state word: timestep (bits 0-7) | context + 6 (bits 8-11: the context is the episode's first action, -5..4, -1 after a
-  // reset — the reference indexes Python lists with it, so -5..-1 are legal and wrap, discounting_chain.py:76-81) | reset_next
-  __device__ static __forceinline__ int dc_context(int32_t st) { return ((st >> 8) & 0xF) - 6; }
-  __device__ static __forceinline__ int32_t dc_pack(int t, int ctx, bool last) {
-    return t | ((ctx + 6) << 8) | (last ? DC_RESET_BIT : 0);
-  }
-  __device__ static __forceinline__ void clear(regs& r) { r.st = dc_pack(0, -1, false); }
-  __device__ static __forceinline__ bool reset_pending(const regs& r) { return (r.st & DC_RESET_BIT) != 0; }
-  __device__ static __forceinline__ void reset_part(const args&, uint64_t, uint64_t, int, unsigned, bsx_reset_pool*) {}
-  __host__ __device__ static bool table_fits(const args&) { return false; }
-  static size_t table_bytes(const args&) { return 0; }
-  __device__ static __forceinline__ bsx_lds_table stage_tables(const args&, float*) { return (bsx_lds_table)0; }
-  template <int V = -1>
-  __device__ static __forceinline__ void load_info(const args&, int64_t, regs&) {}
-  template <int V = -1>
-  __device__ static __forceinline__ void store_info(const args&, int64_t, const regs&) {}
-  __device__ static __forceinline__ void load(const args& a, int64_t i, regs& r) { r.st = a.state[i]; }
-  __device__ static __forceinline__ void store(const args& a, int64_t i, const regs& r) { a.state[i] = r.st; }
-  template <int LOG, int MT, bool IREGS = false, bool TAB = false, bool POOL = false, int V = -1, bool NOFORCE = false>
-  __device__ static __forceinline__ int core(const args& a, regs& rg, const int act, int64_t i, uint64_t, uint64_t,
-                                             float* o, double& reward, bsx_lds_table = (bsx_lds_table)0,
-                                             const bsx_reset_pool* = nullptr) {
-    BSX_NO_CONTRACT
-    const int32_t st = rg.st;
-    int t = st & 0xFF, ctx = dc_context(st);
-    if ((!NOFORCE && a.ctl.force_reset) || (st & DC_RESET_BIT)) {   // discounting_chain.py:69-73
-      o[0] = -1.0f; o[1] = 0.0f;
-      rg.st = dc_pack(0, -1, false);
-      return BSX_FIRST;
-    }
-    if (t == 0) {                                               // :76-77
-      ctx = act;
-      if (ctx < -5 || ctx > 4) {                                // reference: IndexError at the lookup of :80
-        bsx_note_invalid_action(a.ctl, i);
-        ctx = ctx < 0 ? 0 : 4;
-      }
-    }
-    t += 1;
-    const int chain = ctx < 0 ? ctx + 5 : ctx;                  // :80-81 index Python lists: -5..-1 wrap, the context stays negative
-    const int when = chain == 0 ? 1 : chain == 1 ? 3 : chain == 2 ? 10 : chain == 3 ? 30 : 100;   // :49
-    if (t == when) reward = (chain == a.bonus) ? 1.0 + 0.1 : 1.0;                          // :57-58,80-83
-    o[0] = (float)ctx;                                          // :65
-    o[1] = (float)((double)t / 100.0);                          // :66
-    const int type = (t == 100) ? BSX_LAST : BSX_MID;           // :86-88
-    rg.st = dc_pack(t, ctx, type == BSX_LAST);
-    return type;
-  }
-  template <int LOG, int MT>
-  __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t, uint64_t step, float* o, double& reward) {
-    BSX_NO_CONTRACT
-    int32_t st = a.state[i];
-    int t = st & 0xFF, ctx = dc_context(st);
-    if (a.ctl.force_reset || (st & DC_RESET_BIT)) {             // discounting_chain.py:69-73
-      t = 0; ctx = -1;
-      o[0] = -1.0f; o[1] = 0.0f;
-      a.state[i] = dc_pack(0, -1, false);
-      return BSX_FIRST;
-    }
-    if (t == 0) {                                               // :76-77
-      ctx = bsx_action(a.ctl, a.action, oi, step);
-      if (ctx < -5 || ctx > 4) {                                // reference: IndexError at the lookup of :80
-        bsx_note_invalid_action(a.ctl, i);
-        ctx = ctx < 0 ? 0 : 4;                                  // action_spec: 5 values; never OOB
-      }
-    }
-    t += 1;
-    const int chain = ctx < 0 ? ctx + 5 : ctx;                  // :80-81 index Python lists: -5..-1 wrap, the context stays negative
-    const int when = chain == 0 ? 1 : chain == 1 ? 3 : chain == 2 ? 10 : chain == 3 ? 30 : 100;   // :49
-    if (t == when) reward = (chain == a.bonus) ? 1.0 + 0.1 : 1.0;                          // :57-58,80-83
-    o[0] = (float)ctx;                                          // :65
-    o[1] = (float)((double)t / 100.0);                          // :66
-    const int type = (t == 100) ? BSX_LAST : BSX_MID;           // :86-88
-    a.state[i] = dc_pack(t, ctx, type == BSX_LAST);
-    return type;
-  }
-};
-
-// ------------------------------------------------------------------------------ cartpole / swingup
+// The reset flag of the physics families' `steps` word (cartpole, swing-up, mountain_car: step count | flag).
 #define CP_RESET_BIT (1 << 30)
-// Info columns (f64 [4,B]): 0 raw_return, 1 best_episode, 2 episode_return, 3 total_upright.
-// Classic cartpole pays r in {0, 1}: an episode of k steps returns (k-1) + [last step rewarded], so
-// raw_return / best_episode / episode_return are EXACT integer-valued functions of the step counter and
-// are folded into the f64 columns only when the episode ends (column 0 then holds finished episodes;
-// the host adds the running episode's k, environments/cartpole.py).  That removes two f64
-// read-modify-writes (32 B) per lane per step — a third of the step's HBM traffic.  Swing-up's
-// rewards (-0.1*|a-1| + 1) do not sum exactly out of order and the fused Logging rows snapshot the
-// columns mid-episode, so swing-up and logging runs keep the reference's per-step accumulation.
-struct cartpole_env {
-  struct args {
-    bsx_ctl ctl; const int32_t* action; float* state; int32_t* steps; bsx_timestep_t out;
-    double* info; int32_t obs_numel; bsx_cartpole_t cfg;
-    // derived on the host in f64, rounded once (cartpole_make)
-    float inv_m_total, pole_ml, pole_ml_over_mt, den_a, den_b, inv_x_threshold;
-  };
-  // The lane's state in registers: step() = load + core + store; the fused rollout loads once, runs core
-  // T times and stores once (small_obs_body), instead of a round trip through L2 every step.
-  static constexpr bool HAS_REGS = true, PACKED = false, POOLED_RESETS = true, ROWS_VIA_LDS = true;
-  static constexpr int EAGER_LPT_MIN_BLOCKS = 0, EAGER_LPT = 2;      // (equal within noise at 2^20 lanes, 4 % slower at 2^19)
-  // compile-time variants of the lean fused rollout (small_obs_regs_rollout, V): 0 = classic, 1 = swing-up
-  static constexpr int N_VARIANTS = 2;
-  __host__ __device__ static constexpr int numel_of(int v) { return v == 1 ? 8 : 6; }
-  static int variant_of(const args& a) { return a.cfg.swingup ? 1 : 0; }
-  struct regs { float x, xd, th, thd; int32_t sk; double inf[4]; };     // inf: the info columns in a fused rollout
-  // NOFORCE: inside a rollout (n_steps > 1 excludes force_reset: bsx_check_call)
-  template <bool NOFORCE = false>
-  __device__ static __forceinline__ bool wants_reset(const args& a, const regs& r) { return (!NOFORCE && a.ctl.force_reset) || (r.sk & CP_RESET_BIT); }
-  __device__ static __forceinline__ void clear(regs& r) { r.sk = 0; }
-  __device__ static __forceinline__ bool reset_pending(const regs& r) { return (r.sk & CP_RESET_BIT) != 0; }
-  // Half of a lane's reset (cartpole.py:118-128), counter-based stream only: part 0 = x, x_dot from words 0..3 of
-  // the (lane, step) stream, part 1 = theta, theta_dot from words 4..7 and the new angle's sine / cosine — the same
-  // words, the same arithmetic as core()'s in-line reset, one Philox block per part.
-  // (Tried: these parameters in LDS, read where they are used, instead of ten scalar registers live through the
-  // whole step loop — no spill reload left in any variant's loop, but either the Philox key schedule moves to the
-  // vector unit (80 VGPRs) or, with the words read back into scalar registers, the allocator still ends at 68-71
-  // VGPRs instead of 61-65: one reload per step is the cheaper price.)
-  __device__ static __forceinline__ void reset_part(const args& a, uint64_t lane, uint64_t step, int part, unsigned owner,
-                                                    bsx_reset_pool* pool) {
-    BSX_NO_CONTRACT
-    const bsx_cartpole_t& g = a.cfg;
-    bsx_draws d;
-    bsx_draws_init(&d, a.ctl.seed, lane, step, BSX_STREAM_ENV);
-    d.next = 4u * (uint32_t)part;
-    const double lo = -g.init_range, hi = g.init_range;
-    const double w0 = lo + (hi - lo) * bsx_uniform(&d);
-    const double w1 = lo + (hi - lo) * bsx_uniform(&d);
-    const float v0 = (float)(part ? g.theta_offset + w0 : w0), v1 = (float)w1;
-    float si, co;
-    bsx_sincosf(v0, &si, &co);
-    pool->vals[2 * part][owner] = v0;
-    pool->vals[2 * part + 1][owner] = v1;
-    if (part) { pool->vals[4][owner] = si; pool->vals[5][owner] = co; }
-  }
-  // Fused rollouts keep the time-fraction table in LDS when it is small (the default 1002 entries: 4 KiB)
-  static constexpr int TABLE_MAX_BYTES = 16384;
-  __host__ __device__ static bool table_fits(const args& a) { return ((int64_t)a.cfg.last_step + 1) * 4 <= TABLE_MAX_BYTES; }
-  static size_t table_bytes(const args& a) { return table_fits(a) ? ((size_t)a.cfg.last_step + 1) * 4 : 0; }
-  __device__ static __forceinline__ bsx_lds_table stage_tables(const args& a, float* s_dyn) {
-    const int n = a.cfg.last_step + 1;
-    for (int k = threadIdx.x; k < n; k += BSX_BLOCK) s_dyn[k] = a.cfg.time_frac[k];
-    return (bsx_lds_table)s_dyn;
-  }
-  template <int V = -1>
-  __device__ static __forceinline__ void load_info(const args& a, int64_t i, regs& r) {
-    const int64_t B = a.ctl.n_lanes;
-    r.inf[0] = a.info[i]; r.inf[1] = a.info[B + i];
-    if (V >= 0 ? V == 1 : (bool)a.cfg.swingup) { r.inf[2] = a.info[2 * B + i]; r.inf[3] = a.info[3 * B + i]; }
-    else { r.inf[2] = 0.0; r.inf[3] = 0.0; }
-  }
-  template <int V = -1>
-  __device__ static __forceinline__ void store_info(const args& a, int64_t i, const regs& r) {
-    const int64_t B = a.ctl.n_lanes;
-    a.info[i] = r.inf[0]; a.info[B + i] = r.inf[1];
-    if (V >= 0 ? V == 1 : (bool)a.cfg.swingup) { a.info[2 * B + i] = r.inf[2]; a.info[3 * B + i] = r.inf[3]; }
-  }
-  __device__ static __forceinline__ void load(const args& a, int64_t i, regs& r) {
-    const int64_t B = a.ctl.n_lanes;
-    r.sk = a.steps[i];
-    r.x = a.state[i]; r.xd = a.state[B + i]; r.th = a.state[2 * B + i]; r.thd = a.state[3 * B + i];
-  }
-  __device__ static __forceinline__ void store(const args& a, int64_t i, const regs& r) {
-    const int64_t B = a.ctl.n_lanes;
-    a.state[i] = r.x; a.state[B + i] = r.xd; a.state[2 * B + i] = r.th; a.state[3 * B + i] = r.thd;
-    a.steps[i] = r.sk;
-  }
-  template <int LOG, int MT>
-  __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t lane, uint64_t step, float* o, double& reward) {
-    regs r;
-    load(a, i, r);
-    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, oi, step);
-    const int type = core<LOG, MT>(a, r, act, i, lane, step, o, reward);
-    store(a, i, r);
-    return type;
-  }
-  // IREGS: the info columns are rg.inf[] (fused rollout without Logging), else read-modify-written in HBM.
-  // s_tf: the time-fraction table in LDS, or nullptr (-> g.time_frac in device memory).
-  // POOL: the reset values were computed by the workgroup's pool (reset_part) and wait in s_pool.
-  // V: -1 = swing-up or not is a.cfg.swingup, 0 / 1 = known at compile time.  NOFORCE: see wants_reset.
-  template <int LOG, int MT, bool IREGS = false, bool TAB = false, bool POOL = false, int V = -1, bool NOFORCE = false>
-  __device__ static __forceinline__ int core(const args& a, regs& rg, const int act, int64_t i, uint64_t lane, uint64_t step,
-                                             float* o, double& reward, bsx_lds_table s_tf = (bsx_lds_table)0,
-                                             const bsx_reset_pool* s_pool = nullptr) {
-    BSX_NO_CONTRACT
-    const int64_t B = a.ctl.n_lanes;
-    const bsx_cartpole_t& g = a.cfg;
-    const bool swingup = V >= 0 ? V == 1 : (bool)g.swingup;
-    auto info_get = [&](int col) -> double { if constexpr (IREGS) return rg.inf[col]; else return a.info[(int64_t)col * B + i]; };
-    auto info_set = [&](int col, double v) { if constexpr (IREGS) rg.inf[col] = v; else a.info[(int64_t)col * B + i] = v; };
-    const int32_t sk = rg.sk;
-    const bool per_step_info = swingup || LOG == 1 || (LOG == -1 && a.ctl.log.steps != nullptr);
-    int k = sk & 0x3FFFFFFF;
-    float x, xd, th, thd, si, co;
-    int type;
-    if ((!NOFORCE && a.ctl.force_reset) || (sk & CP_RESET_BIT)) {   // cartpole.py:118-128 / swingup:81-91
-      // (Tried, not adopted — profiles/r03/ab_regs_rollout_scalar_reset_draws.log: walking the wave's few resetting
-      // lanes one at a time with wave-uniform inputs puts the Philox rounds on the scalar unit and cuts the vector
-      // instructions by 19 %, but the ~200-instruction dependent scalar chain per resetting lane stalls the wave
-      // longer than the divergent branch did: fused rollout 12.5 -> 14.7 us per step.)
-      if constexpr (POOL) {
-        const unsigned me = threadIdx.x;
-        x = s_pool->vals[0][me]; xd = s_pool->vals[1][me]; th = s_pool->vals[2][me]; thd = s_pool->vals[3][me];
-        si = s_pool->vals[4][me]; co = s_pool->vals[5][me];
-      } else {
-        bsx_draws d;
-        bsx_draws_begin<MT>(&d, a.ctl, i, lane, step);
-        const double lo = -g.init_range, hi = g.init_range;
-        x = (float)(lo + (hi - lo) * bsx_uniform(&d));
-        xd = (float)(lo + (hi - lo) * bsx_uniform(&d));
-        th = (float)(g.theta_offset + (lo + (hi - lo) * bsx_uniform(&d)));
-        thd = (float)(lo + (hi - lo) * bsx_uniform(&d));
-        bsx_draws_end<MT>(&d, a.ctl, i);
-        bsx_sincosf(th, &si, &co);                             // |theta_offset| + init_range <= 32 (cartpole_make)
-      }
-      // an explicit reset() in mid-episode abandons it: the k rewards of 1 it has paid stay in raw_return
-      if (!per_step_info && !(sk & CP_RESET_BIT) && k > 0) info_set(0, info_get(0) + (double)k);
-      k = 0;
-      if (per_step_info) info_set(2, 0.0);                      // _episode_return = 0
-      type = BSX_FIRST;
-    } else {
-      x = rg.x; xd = rg.xd; th = rg.th; thd = rg.thd;
-      // step_cartpole, cartpole.py:37-65, in f32.  One sine/cosine pair per step: that of the OLD
-      // angle; the new angle's pair follows from it by the angle-addition formulas below.
-      float s0, c0;
-      bsx_sincosf(th, &s0, &c0);                                // th is in [0, 2*pi) or a reset value
-      const float force = (float)(act - 1) * g.force_mag;
-      const float temp = (force + a.pole_ml * (thd * thd) * s0) * a.inv_m_total;
-      // theta_acc = (g sin - cos*temp) / (l (4/3 - m_p cos^2 / m_t)); v_rcp_f32 is 1 ulp and the
-      // accelerations enter the state scaled by dt = 0.01
-      const float theta_acc = (g.gravity * s0 - c0 * temp) * __builtin_amdgcn_rcpf(a.den_a - a.den_b * (c0 * c0));
-      const float x_acc = temp - a.pole_ml_over_mt * theta_acc * c0;
-      const float dth = g.timescale * thd;
-      x = __builtin_fmaf(g.timescale, xd, x);
-      xd = __builtin_fmaf(g.timescale, x_acc, xd);
-      // np.remainder(theta + dt*theta_dot, 2*pi) in f64 (the period is not the f32 2*pi): one
-      // conditional +-2*pi is exact (Sterbenz) whenever the sum is within one period of [0, 2*pi)
-      const double raw_ang = (double)th + (double)g.timescale * (double)thd;
-      double ang = raw_ang >= 6.283185307179586 ? raw_ang - 6.283185307179586       // selects, not branches
-                   : (raw_ang < 0.0 ? raw_ang + 6.283185307179586 : raw_ang);
-      if (!(ang >= 0.0 && ang < 6.283185307179586)) {           // |dt*theta_dot| > 2*pi (theta_dot > 600 rad/s:
-        ang = (double)th + (double)g.timescale * (double)thd;   // only reachable from a loaded state)
-        ang -= 6.283185307179586 * floor(ang / 6.283185307179586);
-        if (!(ang >= 0.0 && ang < 6.283185307179586)) ang = 0.0;
-      }
-      th = (float)ang;
-      thd = __builtin_fmaf(g.timescale, theta_acc, thd);
-      if (fabsf(dth) <= 0.5f) bsx_sincos_advance(s0, c0, dth, &si, &co);
-      else bsx_sincosf(th, &si, &co);                           // th is in [0, 2*pi) here
-      k += 1;                                                   // time_elapsed += timescale (:63)
-      const bool timeout = k >= g.last_step;                    // time_elapsed > max_time
-      bool end;
-      double r;
-      if (!swingup) {                                           // cartpole.py:142-153
-        const bool ok = (co > g.height_threshold) && (fabsf(x) < g.x_threshold);
-        r = ok ? 1.0 : 0.0;
-        end = timeout || !ok;
-      } else {                                                  // swingup:104-123
-        const bool up = (co > g.height_threshold) && (fabsf(thd) < g.theta_dot_threshold) &&
-                        (fabsf(x) < g.x_reward_threshold);
-        r = -1.0 * fabs((double)(act - 1)) * g.move_cost;
-        if (up) { r += 1.0; info_set(3, info_get(3) + 1.0); }
-        end = timeout || (fabsf(x) > g.x_threshold);
-      }
-      reward = r;
-      type = end ? BSX_LAST : BSX_MID;
-      if (per_step_info) {
-        info_set(0, info_get(0) + r);                           // _raw_return
-        const double ep = info_get(2) + r;                      // _episode_return
-        info_set(2, ep);
-        if (end) {
-          const double best = info_get(1);
-          info_set(1, ep > best ? ep : best);                   // max(episode_return, best_episode)
-        }
-      } else if (end) {
-        const double ep = (double)(k - 1) + r;                  // sum of the episode's rewards, exact
-        info_set(0, info_get(0) + ep);
-        const double best = info_get(1);
-        info_set(1, ep > best ? ep : best);
-      }
-    }
-    rg.x = x; rg.xd = xd; rg.th = th; rg.thd = thd;
-    rg.sk = k | (type == BSX_LAST ? CP_RESET_BIT : 0);
-    o[0] = x * a.inv_x_threshold;                               // cartpole.py:171-176
-    o[1] = xd * a.inv_x_threshold;
-    o[2] = si;
-    o[3] = co;
-    o[4] = thd;
-    const int kf = k < g.last_step ? k : g.last_step;
-    if constexpr (TAB) o[5] = s_tf[kf];                         // the fused rollout's LDS copy
-    else o[5] = g.time_frac[kf];
-    if (swingup) {                                              // swingup:147-149
-      o[6] = (fabsf(x) < g.x_reward_threshold) ? 1.0f : -1.0f;
-      o[7] = (fabsf(thd) < g.theta_dot_threshold) ? 1.0f : -1.0f;
-    }
-    return type;
-  }
-};
-
-// ------------------------------------------------------------------------------ mountain_car
-// Info column 0 = raw_return = -(steps taken): every step pays -1 (mountain_car.py:75-76), so the
-// column is folded at episode ends (+= -t, exact) and the host subtracts the running episode's t;
-// under the fused Logging wrapper (rows snapshot the column mid-episode) it is kept per step.
-struct mountain_car_env {
-  struct args {
-    bsx_ctl ctl; const int32_t* action; float* state; int32_t* steps; bsx_timestep_t out;
-    double* info; int32_t obs_numel; int32_t max_steps;
-  };
-  // (resets are rare — 1000-step episodes — and one Philox block: not pooled; the 12-byte rows of a wave are one dense
-  // 768-byte range already: staging them gained nothing, profiles/r03/ab_rows_via_lds.log)
-  static constexpr bool HAS_REGS = true, PACKED = false, POOLED_RESETS = false, ROWS_VIA_LDS = false;
-  static constexpr int EAGER_LPT_MIN_BLOCKS = 2048, EAGER_LPT = 2;
-  static constexpr int N_VARIANTS = 1;
-  __host__ __device__ static constexpr int numel_of(int) { return 3; }
-  static int variant_of(const args&) { return 0; }
-  struct regs { float pos, vel; int32_t sk; double inf0; };             // inf0: raw_return in a fused rollout
-  template <bool NOFORCE = false>
-  __device__ static __forceinline__ bool wants_reset(const args&, const regs&) { return false; }
-  __device__ static __forceinline__ void clear(regs& r) { r.sk = 0; }
-  __device__ static __forceinline__ bool reset_pending(const regs& r) { return (r.sk & CP_RESET_BIT) != 0; }
-  __device__ static __forceinline__ void reset_part(const args&, uint64_t, uint64_t, int, unsigned, bsx_reset_pool*) {}
-  // Fused rollouts read the time fraction t / max_steps (an f32 division: 11 of the step's ~95 vector instructions)
-  // from a table in LDS that the workgroup fills once per launch with that same division.
-  static constexpr int TABLE_MAX_BYTES = 16384;
-  __host__ __device__ static bool table_fits(const args& a) { return ((int64_t)a.max_steps + 1) * 4 <= TABLE_MAX_BYTES; }
-  static size_t table_bytes(const args& a) { return table_fits(a) ? ((size_t)a.max_steps + 1) * 4 : 0; }
-  __device__ static __forceinline__ bsx_lds_table stage_tables(const args& a, float* s_dyn) {
-    for (int k = threadIdx.x; k <= a.max_steps; k += BSX_BLOCK) s_dyn[k] = (float)k / (float)a.max_steps;
-    return (bsx_lds_table)s_dyn;
-  }
-  template <int V = -1>
-  __device__ static __forceinline__ void load_info(const args& a, int64_t i, regs& r) { r.inf0 = a.info[i]; }
-  template <int V = -1>
-  __device__ static __forceinline__ void store_info(const args& a, int64_t i, const regs& r) { a.info[i] = r.inf0; }
-  __device__ static __forceinline__ void load(const args& a, int64_t i, regs& r) {
-    r.sk = a.steps[i]; r.pos = a.state[i]; r.vel = a.state[a.ctl.n_lanes + i];
-  }
-  __device__ static __forceinline__ void store(const args& a, int64_t i, const regs& r) {
-    a.state[i] = r.pos; a.state[a.ctl.n_lanes + i] = r.vel; a.steps[i] = r.sk;
-  }
-  template <int LOG, int MT>
-  __device__ static int step(const args& a, int64_t i, int64_t oi, uint64_t lane, uint64_t step, float* o, double& reward) {
-    regs r;
-    load(a, i, r);
-    const int act = a.ctl.force_reset ? 0 : bsx_action(a.ctl, a.action, oi, step);
-    const int type = core<LOG, MT>(a, r, act, i, lane, step, o, reward);
-    store(a, i, r);
-    return type;
-  }
-  template <int LOG, int MT, bool IREGS = false, bool TAB = false, bool POOL = false, int V = -1, bool NOFORCE = false>
-  __device__ static __forceinline__ int core(const args& a, regs& rg, const int act, int64_t i, uint64_t lane, uint64_t step,
-                                             float* o, double& reward, bsx_lds_table s_tf = (bsx_lds_table)0,
-                                             const bsx_reset_pool* = nullptr) {
-    BSX_NO_CONTRACT
-    const int32_t sk = rg.sk;
-    int t = sk & 0x3FFFFFFF;
-    auto info_add = [&](double v) { if constexpr (IREGS) rg.inf0 += v; else a.info[i] += v; };
-    float pos, vel;
-    int type;
-    if ((!NOFORCE && a.ctl.force_reset) || (sk & CP_RESET_BIT)) {   // mountain_car.py:66-71
-      bsx_draws d;
-      bsx_draws_begin<MT>(&d, a.ctl, i, lane, step);
-      // an explicit reset() in mid-episode abandons it: its t rewards of -1 stay in raw_return
-      if (!(LOG == 1 || (LOG == -1 && a.ctl.log.steps != nullptr)) && !(sk & CP_RESET_BIT) && t > 0) info_add(-(double)t);
-      t = 0;
-      pos = (float)(-0.6 + (-0.4 - -0.6) * bsx_uniform(&d));
-      bsx_draws_end<MT>(&d, a.ctl, i);
-      vel = 0.0f;
-      type = BSX_FIRST;
-    } else {
-      pos = rg.pos; vel = rg.vel;
-      t += 1;                                                   // :74
-      reward = -1.0;
-      float sn, cs;
-      bsx_sincosf(3.0f * pos, &sn, &cs);                        // position is clipped to [-1.2, 0.6]
-      vel += (float)(act - 1) * 0.001f + cs * -0.0025f;            // :79-80
-      vel = fminf(fmaxf(vel, -0.07f), 0.07f);                   // :81
-      pos += vel;                                               // :82
-      pos = fminf(fmaxf(pos, -1.2f), 0.6f);                     // :83
-      if (pos == -1.2f) vel = fminf(fmaxf(vel, 0.0f), 0.07f);   // :84-85
-      type = (pos >= 0.5f || t >= a.max_steps) ? BSX_LAST : BSX_MID;   // :88-90
-      if (LOG == 1 || (LOG == -1 && a.ctl.log.steps != nullptr)) info_add(reward);   // :76, per step under Logging
-      else if (type == BSX_LAST) info_add(-(double)t);          // the episode's t rewards of -1, exact
-    }
-    rg.pos = pos; rg.vel = vel;
-    rg.sk = t | (type == BSX_LAST ? CP_RESET_BIT : 0);
-    o[0] = pos;                                                 // :62-64
-    o[1] = vel;
-    if constexpr (TAB) o[2] = s_tf[t];                          // (t <= max_steps)
-    else o[2] = (float)t / (float)a.max_steps;                  // both exact in f32; correctly rounded quotient
-    return type;
-  }
-};
-// (with its 12-byte rows non-temporal, mountain_car's rollout is faster with ORDINARY scalar stores: 4.45 against 4.7 us per step)
-template <> struct small_rollout_nt_scalars<mountain_car_env> { static constexpr bool value = false; };
 
 #endif  // BSX_SMALL_OBS_H_

@@ -1,4 +1,5 @@
-// small_obs.hip — what the small-observation families share on the host side (device code: small_obs.h); their C-ABI entry
+// small_obs.hip — what the small-observation families share on the host side (the kernel skeleton: small_obs.h, a family's
+// device code: <family>_env.h); their C-ABI entry
 // points live one file per family (bandit.hip, memory_chain.hip, umbrella_chain.hip, discounting_chain.hip, cartpole.hip,
 // mountain_car.hip):
 //   bandit            bsuite/environments/bandit.py:54-64
@@ -9,7 +10,8 @@
 //                     bsuite/experiments/cartpole_swingup/cartpole_swingup.py:81-150
 //   mountain_car      bsuite/environments/mountain_car.py:62-90
 // each with the auto-reset of bsuite/environments/base.py:54-65.
-#include "small_obs.h"
+#include "bsx_device.h"
+#include "bsx_rows.h"
 
 // Tile class of a segment inside a grouped launch (segments of one group must share it).  Always 256 since
 // the bit-plane tiles: the 64-lane class for rows wider than 32 floats is gone (kept in the ABI so that a

@@ -3,7 +3,18 @@
 //   BSX_FAM_SWEEP_MIXED   phase 0: every lane of EVERY family advanced by one launch (the lane advance of
 //                         deep_sea / catch / mnist + the whole step of the small-observation families), and the
 //                         software-pipelined form: that phase beside the previous step's observation store stream.
+#include "bandit_env.h"
+#include "bsx_pair_device.h"
+#include "cartpole_env.h"
+#include "catch_fam.h"
+#include "deep_sea_fam.h"
+#include "discounting_chain_env.h"
+#include "memory_chain_env.h"
+#include "mnist_fam.h"
+#include "mountain_car_env.h"
+#include "pair_mixed.h"
 #include "small_obs.h"
+#include "umbrella_chain_env.h"
 
 // ------------------------------------------------------------------------------ mixed-family group
 __global__ void __launch_bounds__(BSX_BLOCK) small_obs_mixed_group_kernel(const uint8_t* __restrict__ table,

@@ -1,4 +1,4 @@
-"""Batched SimpleBandit (counterpart of bsuite/environments/bandit.py; kernel: csrc/small_obs.hip)."""
+"""Batched SimpleBandit (counterpart of bsuite/environments/bandit.py; kernel: csrc/bandit_env.h on the skeleton of csrc/small_obs.h)."""
 import ctypes
 from typing import Optional
 

@@ -1,5 +1,5 @@
 """Batched Cartpole and CartpoleSwingup (counterparts of bsuite/environments/cartpole.py and
-bsuite/experiments/cartpole_swingup/cartpole_swingup.py; kernel: csrc/small_obs.hip).
+bsuite/experiments/cartpole_swingup/cartpole_swingup.py; kernel: csrc/cartpole_env.h on the skeleton of csrc/small_obs.h).
 
 Device state is f32 (the reference holds Python floats); `time_elapsed` is kept as an integer step
 count k, with the reference's f64 running sum `time_elapsed += timescale` (cartpole.py:63) replayed
@@ -88,7 +88,7 @@ class Cartpole(_CartpoleBase):
   def _pending_info(self):
     # Rewards are 1 on every step that does not end the episode (cartpole.py:142-149), so a running
     # episode of k steps has earned exactly k; the kernel folds (k-1) + last reward into raw_return /
-    # best_episode when the episode ends (csrc/small_obs.hip, cartpole_env).
+    # best_episode when the episode ends (csrc/cartpole_env.h).
     steps = self._state['steps']
     running = (steps & (1 << 30)) == 0
     k = torch.where(running, steps & 0x3FFFFFFF, torch.zeros_like(steps)).to(torch.float64)

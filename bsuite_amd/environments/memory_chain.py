@@ -1,4 +1,4 @@
-"""Batched MemoryChain (counterpart of bsuite/environments/memory_chain.py; csrc/small_obs.hip)."""
+"""Batched MemoryChain (counterpart of bsuite/environments/memory_chain.py; kernel: csrc/memory_chain_env.h on the skeleton of csrc/small_obs.h)."""
 import ctypes
 from typing import Optional
 

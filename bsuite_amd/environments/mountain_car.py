@@ -1,4 +1,4 @@
-"""Batched MountainCar (counterpart of bsuite/environments/mountain_car.py; csrc/small_obs.hip)."""
+"""Batched MountainCar (counterpart of bsuite/environments/mountain_car.py; kernel: csrc/mountain_car_env.h on the skeleton of csrc/small_obs.h)."""
 import ctypes
 from typing import Optional
 
@@ -32,7 +32,7 @@ class MountainCar(base.Environment):
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the
-    # kernel folds it into raw_return when the episode ends (csrc/small_obs.hip, mountain_car_env)
+    # kernel folds it into raw_return when the episode ends (csrc/mountain_car_env.h)
     steps = self._state['steps']
     running = (steps & (1 << 30)) == 0
     return {0: -torch.where(running, steps & 0x3FFFFFFF, torch.zeros_like(steps)).to(torch.float64)}

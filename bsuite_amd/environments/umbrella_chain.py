@@ -1,4 +1,4 @@
-"""Batched UmbrellaChain (counterpart of bsuite/environments/umbrella_chain.py; csrc/small_obs.hip)."""
+"""Batched UmbrellaChain (counterpart of bsuite/environments/umbrella_chain.py; kernel: csrc/umbrella_chain_env.h on the skeleton of csrc/small_obs.h)."""
 import ctypes
 from typing import Optional
 

@@ -490,7 +490,7 @@ int bsx_group_set_mnist(bsx_group_t* g, int32_t index, const bsx_mnist_t* cfg, c
                         const int32_t* action, int32_t* state, bsx_timestep_t out, double* info);
 /* Tile class (lanes per workgroup) a small-observation segment with `numel` observation floats gets
  * inside a group; segments of one group must share it.  Since ABI v9 always 256: the wide rows are
- * staged as bit planes (bsuite_amd/csrc/small_obs.hip), the 64-lane class is gone. */
+ * staged as bit planes (bsuite_amd/csrc/small_obs.h), the 64-lane class is gone. */
 int bsx_group_small_class(int32_t numel);
 int bsx_group_commit(bsx_group_t* g);
 int bsx_group_step(bsx_group_t* g, void* hip_stream);

@@ -93,7 +93,7 @@ def test_catch_full_batch():
 @pytest.mark.parametrize('form', ['eager', 'rollout', 'eager_logging'])
 def test_catch_wrapped_full_batch(form):
   """catch_noise at B = 2^20: a WRAPPED step (RewardNoise; with the Logging bookkeeping in `eager_logging`) is ONE fused launch up to
-  this size since round 6 (bsx_host.h: BSX_FUSED_WRAPPED_MAX_MIB), where the lean step is the decoupled pair — a 4096-lane
+  this size since round 6 (bsx_pair_host.h: BSX_FUSED_WRAPPED_MAX_MIB), where the lean step is the decoupled pair — a 4096-lane
   subsample against the oracle bit for bit on every step (f64 noise draws included), one-hot invariants on all lanes."""
   T, seed, sigma = 24, 11, 0.3
   env = eu.make_env('catch', dict(), batch=B, lane_offset=0, seed=seed, wrap=('noise', sigma), num_buffers=1)

@@ -91,7 +91,7 @@ def test_lean_rollout_step_loops_reload_no_spilled_scalars():
   import kernel_isa as ki
   csrc = os.path.join(ROOT, 'bsuite_amd', 'csrc')
   # kernel -> most reloads in its step loop.  Swing-up (two more thresholds, an f64 move cost, per-step info columns in
-  # registers) still reloads ~20 scalars per step; taking them out cost 6-15 VGPRs in every variant tried (small_obs.h)
+  # registers) still reloads ~20 scalars per step; taking them out cost 6-15 VGPRs in every variant tried (cartpole_env.h)
   for want, most in (('small_obs_lean_rollout_kernel<cartpole_env, true, 0, true>', 0), ('small_obs_lean_rollout_kernel<cartpole_env, false, 0, true>', 0),
                      ('small_obs_lean_rollout_kernel<mountain_car_env, false, 0, true>', 0),
                      ('small_obs_lean_rollout_kernel<cartpole_env, true, 1, true>', 24), ('small_obs_lean_rollout_kernel<cartpole_env, false, 1, true>', 24)):

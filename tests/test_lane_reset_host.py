@@ -205,7 +205,9 @@ def test_marked_words_against_hand_derived_values(shim, family, variant, folded,
 
 def test_reset_bits_are_the_kernels_own(shim):
   """The bit positions in bsx_lane_reset.h against the *_RESET_BIT macros the step kernels test."""
-  text = ''.join(open(os.path.join(CSRC, f)).read() for f in ('deep_sea_fam.h', 'catch_fam.h', 'mnist_fam.h', 'small_obs.h'))
+  text = ''.join(open(os.path.join(CSRC, f)).read() for f in ('deep_sea_fam.h', 'catch_fam.h', 'mnist_fam.h', 'small_obs.h', 'bandit_env.h',
+                           'memory_chain_env.h', 'umbrella_chain_env.h', 'discounting_chain_env.h', 'cartpole_env.h',
+                           'mountain_car_env.h'))
   macros = {m: 1 << int(s) for m, s in re.findall(r'#define (\w+_RESET_BIT) \(1 << (\d+)\)', text)}
   want = dict(deep_sea='DS', catch='CATCH', memory_chain='MC', umbrella_chain='UC', discounting_chain='DC', cartpole='CP',
               mountain_car='CP', mnist='MN')

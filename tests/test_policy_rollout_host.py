@@ -421,7 +421,7 @@ def test_the_kernels_use_the_header(shim):
   """The device code calls the functions the shim has just checked, and tests the reset bits the step kernels test."""
   del shim
   csrc = os.path.join(ROOT, 'bsuite_amd', 'csrc')
-  dev = open(os.path.join(csrc, 'bsx_device.h')).read()
+  dev = open(os.path.join(csrc, 'bsx_pair_device.h')).read()
   body = dev[dev.index('bsx_policy_rollout_kernel('):]
   body = body[:body.index('\n}\n')]
   for call_ in ('fn.policy_key(st)', 'bsx_policy_clamp(', 'bsx_policy_draws(p.explore_seed, lane, step)', 'bsx_policy_select(', 'Fam::resets(st)'):
