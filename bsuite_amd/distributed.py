@@ -15,6 +15,8 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from bsuite_amd.environments.base import raw as _raw
+
 
 def shard_lanes(total_lanes: int, rank: int, world_size: int) -> Tuple[int, int]:
   """Contiguous lane range of `rank`: returns (lane_offset, n_lanes).  Remainder lanes go to the
@@ -29,7 +31,7 @@ def shard_lanes(total_lanes: int, rank: int, world_size: int) -> Tuple[int, int]
 
 def local_summary(env) -> Tuple[torch.Tensor, Tuple[str, ...]]:
   """f64 vector [lanes, episodes_finished, episodes_started, sum(info_k)...] for this shard."""
-  raw = env.raw_env if hasattr(env, 'raw_env') else env
+  raw = _raw(env)
   counters = raw.episode_counters().to(torch.float64)
   info = env.bsuite_info()
   keys = tuple(sorted(info))

@@ -1,5 +1,4 @@
 """Batched SimpleBandit (counterpart of bsuite/environments/bandit.py; kernel: csrc/bandit_env.h on the skeleton of csrc/small_obs.h)."""
-import ctypes
 from typing import Optional
 
 import numpy as np
@@ -36,9 +35,6 @@ class SimpleBandit(base.Environment):
     return dict(state=torch.ones(self._batch, dtype=torch.int32, device=self._device))
 
   _abi_name = 'bandit'
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())
 
   def _check_scalar_action(self, action):
     self._rewards[action]  # IndexError where bandit.py:61 raises it  pylint: disable=pointless-statement

@@ -54,6 +54,26 @@ _OBS_SPEC_DTYPES = {torch.float32: np.float32, torch.uint8: np.uint8, torch.floa
                     torch.int32: np.int32}          # observation_mode='index' (never an observation_dtype a caller may pass)
 
 
+# The standard columns of a Logging snapshot row, in row order (STANDARD_KEYS, wrappers.py:30-31); the per-lane
+# accumulators of enable_logging() carry the same names.
+LOGGING_COLUMNS = ('steps', 'episode', 'total_return', 'episode_len', 'episode_return')
+
+# The per-lane columns of np.random.RandomState's state (rng='mt19937'), in the order of bsx_stream_t / bsx_reward_wrap_t.
+_MT_COLUMNS = ('state', 'pos', 'gauss', 'has_gauss')
+
+
+def raw(env):
+  """The engine environment under a stack of wrappers (`env` itself when it is none).  Only wrappers have `raw_env`:
+  that is how callers tell the two apart."""
+  return env.raw_env if hasattr(env, 'raw_env') else env
+
+
+def _timestep_ptrs(o) -> '_native.TimeStepPtrs':
+  """bsx_timestep_ptrs_t over a dict of reward / discount / step_type / observation tensors."""
+  return _native.TimeStepPtrs(o['reward'].data_ptr(), o['discount'].data_ptr(), o['step_type'].data_ptr(),
+                              o['observation'].data_ptr())
+
+
 def _resolve_seed(seed: Optional[int]) -> int:
   """seed=None means fresh OS entropy, as np.random.RandomState(None) does in the reference."""
   if seed is None:
@@ -72,7 +92,6 @@ class Environment(dm_env.EnvironmentBase):
   _supports_narrow_obs = False  # families whose observations are all 0/1: observation_dtype may be narrower than float32
   _index_width = 0  # observation_mode='index': int32 values per lane (bsx_observation_index_width), 0 = the family has no such mode
   _pipelined_rollout = False  # two-kernel families whose rollouts are software-pipelined (state_alt)
-  _state_alt = None
   scalar_host_buffers = True   # scalar view: TimeStep / action buffers in pinned host memory mapped into the device (class
                                # attribute: set False before the first step to A/B against device buffers + read-backs)
   # memory_chain / umbrella_chain with a row of more than 8 floats: from this many bytes of observations per step() a call
@@ -84,7 +103,6 @@ class Environment(dm_env.EnvironmentBase):
   # one launch needs for advance AND stores once other workgroups' stores hide behind it.  Kept as an option (tests,
   # A/B: bench.py --row-path on).
   row_path_min_bytes = None
-  _rows = None
   # Families with a single-launch step (deep_sea): the bit of the packed state word that carries the parity of the
   # call index that reads the word next, and all the bits of the word that are the library's bookkeeping (never part of a
   # state_dict).  The flag BSX_CALL_STATE_TAGGED is only set where every call index is exactly the previous one plus 1 —
@@ -99,6 +117,8 @@ class Environment(dm_env.EnvironmentBase):
   _tag_calls = False
   _info_keys = ()          # names of the f64 info columns, in native column order
   _info_int_keys = ()      # keys the reference reports as Python ints
+  _abi_name = None         # family name in the C ABI (bsx_<name>_step / bsx_group_set_<name>)
+  _cfg = None              # the family's bsx_<name>_cfg_t (a ctypes structure of _native), set by the subclass constructor
 
   def __init__(self, obs_shape, num_actions, *, seed=None, batch=None, device=None,
                lane_offset=0, num_buffers=2, device_step_counter=False, shared_step_counter=None,
@@ -126,10 +146,42 @@ class Environment(dm_env.EnvironmentBase):
     # obs_allocator(shape) -> float32 device tensor: lets a caller that owns many environments (SweepBatch)
     # place all their observation buffers in one arena, in launch order, each on a 4 KiB boundary.
     self._obs_allocator = obs_allocator
+    self._resolve_observations(observation_mode, observation_dtype)
     # rng='mt19937': every lane carries the reference's own generator (np.random.RandomState(seed),
     # MT19937 + numpy's legacy samplers) in HBM, so seeded runs reproduce the reference without any
     # replay shim.  `seed` may be a sequence of B seeds; an int s seeds lane i with
     # s + i.  2.5 KB of state per lane: meant for small batches.
+    if rng not in ('philox', 'mt19937'):
+      raise ValueError("rng must be 'philox' or 'mt19937'")
+    self._rng_mode = rng
+    self._mt_seeds = None
+    if rng == 'mt19937':
+      if seed is None or isinstance(seed, (int, np.integer)):
+        self._mt_seeds = [(self._seed + i) & 0xFFFFFFFF for i in range(self._batch)]
+      else:
+        self._mt_seeds = [int(x) for x in seed]
+        if len(self._mt_seeds) != self._batch:
+          raise ValueError('need one seed per lane')
+    self._wrap = (_native.WRAP_NONE, 0.0, 0, 0.0)   # fused reward epilogue: kind, param, wrapper seed, param2
+    self._wrap_mt_seeds = None         # rng='mt19937' + RewardNoise: the wrapper's own RandomState seeds
+    self._wrap_mt = None
+    self._logging = None
+    self._deferred_steps = None
+    self._grouped_by = None            # the SweepBatch whose prepared groups hold this environment's column pointers
+    self._rollout_out = {}             # rollout() / rollout_policy(): output buffers per T (_new_outputs)
+    self._policy_rollout_out = {}
+    self._state_alt = None             # pipelined rollouts: the scratch state column (allocated on first use)
+    self._row_buf = None               # the row scratch of _row_scratch() (allocated on first use)
+    self._dev_index = self._device.index
+    self._step_index = 0
+    self._buf = 0
+    self._allocated = False
+    self._reset_next_step = True       # base.py:52 (every lane starts with its reset flag set)
+
+  def _resolve_observations(self, observation_mode, observation_dtype):
+    """Checks `observation_mode` and `observation_dtype` against the family, the view and each other, before any GPU
+    use, and fixes what follows from them: `_delta`, `_index`, `_board_shape`, and the shape, dtype and
+    bsx_call_t.flags element code of the observations the kernels write."""
     # observation_mode='delta' (deep_sea, catch): the engine keeps its observation buffers persistent
     # and per call only clears the cells that went stale and sets the new hot cells (a few 4-byte
     # stores per lane instead of the whole board).  The tensors returned are identical to the dense
@@ -152,7 +204,7 @@ class Environment(dm_env.EnvironmentBase):
         raise ValueError(f'{type(self).__name__} has no index observation mode (its observations are not one-hot boards)')
       if self._scalar:
         raise ValueError("observation_mode='index' needs the batched view (batch=B)")
-      if obs_allocator is not None:
+      if self._obs_allocator is not None:
         raise ValueError("observation_mode='index' is not available in SweepBatch (float32 arenas)")
     # observation_dtype (deep_sea, catch): the element type the engine writes its observations in — float32, or uint8 /
     # float16 / bfloat16, which hold the boards' 0.0 and 1.0 exactly in a quarter / half of the bytes.  Batched, dense,
@@ -167,7 +219,7 @@ class Environment(dm_env.EnvironmentBase):
         raise ValueError('observation_dtype other than float32 needs the batched view (batch=B)')
       if self._delta:
         raise ValueError("observation_dtype other than float32 needs observation_mode='dense'")
-      if obs_allocator is not None:
+      if self._obs_allocator is not None:
         raise ValueError('observation_dtype other than float32 is not available in SweepBatch (float32 arenas)')
     if self._index and dt != torch.float32:
       raise ValueError("observation_mode='index' writes int32 cell numbers: observation_dtype must stay float32")
@@ -176,26 +228,6 @@ class Environment(dm_env.EnvironmentBase):
     if self._index:           # from here on the observation IS the [K] int32 row; board_shape keeps the dense shape
       self._obs_shape, self._obs_dtype = (self._index_width,), torch.int32
       self._obs_flags = _native.CALL_OBS_INDEX
-    if rng not in ('philox', 'mt19937'):
-      raise ValueError("rng must be 'philox' or 'mt19937'")
-    self._rng_mode = rng
-    self._mt_seeds = None
-    if rng == 'mt19937':
-      if seed is None or isinstance(seed, (int, np.integer)):
-        self._mt_seeds = [(self._seed + i) & 0xFFFFFFFF for i in range(self._batch)]
-      else:
-        self._mt_seeds = [int(x) for x in seed]
-        if len(self._mt_seeds) != self._batch:
-          raise ValueError('need one seed per lane')
-    self._wrap = (_native.WRAP_NONE, 0.0, 0, 0.0)   # fused reward epilogue: kind, param, wrapper seed, param2
-    self._wrap_mt_seeds = None         # rng='mt19937' + RewardNoise: the wrapper's own RandomState seeds
-    self._wrap_mt = None
-    self._logging = None
-    self._deferred_steps = None
-    self._step_index = 0
-    self._buf = 0
-    self._allocated = False
-    self._reset_next_step = True       # base.py:52 (every lane starts with its reset flag set)
 
   # ----------------------------------------------------------------------------------------
   # device buffers
@@ -264,11 +296,13 @@ class Environment(dm_env.EnvironmentBase):
     """Subclass hook: allocate the family's SoA state columns with their initial values."""
     raise NotImplementedError
 
-  _abi_name = None   # subclass: family name in the C ABI (bsx_<name>_step / bsx_group_set_<name>)
-
   def _native_args(self, call, action_ptr, out):
-    """Subclass hook: the argument tuple of bsx_<family>_step for this environment."""
-    raise NotImplementedError
+    """The argument tuple of bsx_<family>_step (and, after group and index, of bsx_group_set_<family>): configuration,
+    call descriptor, actions, the state columns in `_state_tensors()` order, outputs and — families with `_info_keys` —
+    the info columns."""
+    state = tuple(t.data_ptr() for t in self._state.values())
+    info = (self._info.data_ptr(),) if self._info_keys else ()
+    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr) + state + (out,) + info
 
   def _launch(self, call, action_ptr, out) -> int:
     """Calls the family's C-ABI entry point."""
@@ -302,14 +336,11 @@ class Environment(dm_env.EnvironmentBase):
       raise ValueError('grouped launches write float32 observations; use observation_dtype=torch.float32')
     call = self._call_desc
     call.force_reset, call.n_steps = 0, 0
-    kind, param, wseed, param2 = self._wrap
-    call.wrap.kind, call.wrap.param, call.wrap.seed, call.wrap.param2 = kind, param, wseed, param2
-    self._wrap_applied = self._wrap
+    self._sync_wrap()
     call.stream.step_index = 0
     call.action_ring = ring
     self._buf = 1 % self._num_buffers
-    ptrs = self._out_ptrs[0] if out is None else _native.TimeStepPtrs(
-        out['reward'].data_ptr(), out['discount'].data_ptr(), out['step_type'].data_ptr(), out['observation'].data_ptr())
+    ptrs = self._out_ptrs[0] if out is None else _timestep_ptrs(out)
     own = self._state.get('state')
     own_rows = call.row_scratch
     if row_scratch is not None:                # whole-sweep groups: the chains' wide rows go through the group's store stream
@@ -340,13 +371,13 @@ class Environment(dm_env.EnvironmentBase):
     words = self._row_scratch_words()
     if not words:
       return None
-    if fresh or self._rows is None:
+    if fresh or self._row_buf is None:
       with torch.cuda.device(self._device):
         t = torch.empty(words, dtype=torch.int32, device=self._device)
       if fresh:
         return t
-      self._rows = t
-    return self._rows
+      self._row_buf = t
+    return self._row_buf
 
   def _set_wrap_mt_seeds(self, seeds):
     """rng='mt19937': RewardNoise's own np.random.RandomState(seed) per lane (wrappers.py:267)."""
@@ -368,16 +399,14 @@ class Environment(dm_env.EnvironmentBase):
         prepare(rs)
       _, key, p, hg, cg = rs.get_state()
       keys[i], pos[i], has[i], gauss[i] = key, p, hg, cg
-    return dict(state=torch.from_numpy(np.ascontiguousarray(keys.T).view(np.int32)).to(device),
-                pos=torch.from_numpy(pos).to(device), gauss=torch.from_numpy(gauss).to(device),
-                has_gauss=torch.from_numpy(has).to(device))
+    cols = (np.ascontiguousarray(keys.T).view(np.int32), pos, gauss, has)
+    return {k: torch.from_numpy(v).to(device) for k, v in zip(_MT_COLUMNS, cols)}
 
   def _upload_wrap_mt(self):
     with torch.cuda.device(self._device):
       self._wrap_mt = self._mt_columns(self._wrap_mt_seeds, self._device)
-    w = self._call_desc.wrap
-    w.mt_state, w.mt_pos = self._wrap_mt['state'].data_ptr(), self._wrap_mt['pos'].data_ptr()
-    w.mt_gauss, w.mt_has_gauss = self._wrap_mt['gauss'].data_ptr(), self._wrap_mt['has_gauss'].data_ptr()
+    for k, v in self._wrap_mt.items():
+      setattr(self._call_desc.wrap, 'mt_' + k, v.data_ptr())
 
   def _mt_constructor_draws(self, rs: np.random.RandomState):
     """Subclass hook (rng='mt19937'): consume from `rs` exactly what the reference constructor
@@ -399,25 +428,21 @@ class Environment(dm_env.EnvironmentBase):
                                    dtype=torch.int64, device=dev)
       self._step_base = (self._shared_step_counter if self._shared_step_counter is not None
                          else torch.zeros(1, dtype=torch.int64, device=dev))
-      self._out = []
-      self._out_ptrs = []
       # Scalar view: TimeStep buffers and the action live in pinned host memory, which HIP maps into
       # the device address space — the kernels write the TimeStep straight into host RAM and a step
       # costs one stream synchronisation instead of a fill kernel + four device-to-host reads.
       self._host_out = self._scalar and self.scalar_host_buffers
       place = dict(pin_memory=True) if self._host_out else dict(device=dev)
+      bufs = []
       for _ in range(self._num_buffers):
-        o = dict(
-            reward=torch.empty(B, dtype=torch.float32, **place),
-            discount=torch.empty(B, dtype=torch.float32, **place),
-            step_type=torch.empty(B, dtype=torch.int8, **place),
-            observation=(self._obs_allocator((B,) + self._obs_shape)
-                         if (self._obs_allocator is not None and not self._scalar and not self._delta) else
-                         (torch.zeros if self._delta else torch.empty)((B,) + self._obs_shape, dtype=self._obs_dtype, **place)))
-        self._out.append(o)
-        self._out_ptrs.append(_native.TimeStepPtrs(
-            o['reward'].data_ptr(), o['discount'].data_ptr(), o['step_type'].data_ptr(),
-            o['observation'].data_ptr()))
+        obs = None
+        if self._obs_allocator is not None and not self._scalar and not self._delta:
+          obs = self._obs_allocator((B,) + self._obs_shape)
+        elif self._delta:               # persistent boards: they start all-zero and the kernels only touch the hot cells
+          obs = torch.zeros((B,) + self._obs_shape, dtype=self._obs_dtype, **place)
+        bufs.append(self._new_outputs((B,), place, obs))
+      self._out, self._out_ptrs = [o for o, _, _ in bufs], [p for _, p, _ in bufs]
+      self._timesteps = None if self._scalar else [ts for _, _, ts in bufs]    # what the batched view returns
       # delta mode: per buffer, the packed state whose hot cells the buffer currently shows (-1: none)
       self._paint = ([torch.full((B,), -1, dtype=torch.int32, device=dev) for _ in range(self._num_buffers)]
                      if self._delta else None)
@@ -425,21 +450,18 @@ class Environment(dm_env.EnvironmentBase):
       # scalar view: the reward as the f64 the reference returns (not its f32 rounding)
       self._reward_f64 = torch.zeros(1, dtype=torch.float64, **place) if self._scalar else None
       self._out_np = [{k: v.numpy() for k, v in o.items()} for o in self._out] if self._host_out else None
-    mt_state_ptr = mt_pos_ptr = mt_gauss_ptr = mt_has_ptr = None
+    self._mt = None                    # rng='mt19937': the lanes' generator columns ([624, B] key words, [B] pos, ...)
     if self._rng_mode == 'mt19937':
       with torch.cuda.device(dev):
         # initial states built by numpy itself, after the draws each reference constructor makes
-        cols = self._mt_columns(self._mt_seeds, dev, prepare=self._mt_constructor_draws)
-      self._mt_state, self._mt_pos = cols['state'], cols['pos']              # [624, B], [B]
-      self._mt_gauss, self._mt_has_gauss = cols['gauss'], cols['has_gauss']
-      mt_state_ptr, mt_pos_ptr = self._mt_state.data_ptr(), self._mt_pos.data_ptr()
-      mt_gauss_ptr, mt_has_ptr = self._mt_gauss.data_ptr(), self._mt_has_gauss.data_ptr()
+        self._mt = self._mt_columns(self._mt_seeds, dev, prepare=self._mt_constructor_draws)
+    mt_ptrs = [self._mt[k].data_ptr() if self._mt else None for k in _MT_COLUMNS]
     # One persistent call descriptor: only step_index / force_reset / stream change per call.
     self._call_desc = _native.Call(
         n_lanes=B, force_reset=0,
         stream=_native.Stream(self._seed, self._lane_offset, 0,
                               self._step_base.data_ptr() if self._device_step_counter else None,
-                              mt_state_ptr, mt_pos_ptr, mt_gauss_ptr, mt_has_ptr),
+                              *mt_ptrs),
         wrap=_native.RewardWrap(_native.WRAP_NONE, 0, 0.0, 0, None, None, None, None, 0.0),
         counters=self._counters.data_ptr(), hip_stream=None)
     if self._reward_f64 is not None:
@@ -466,21 +488,42 @@ class Environment(dm_env.EnvironmentBase):
       self._call_desc.flags = _native.CALL_STATE_TAGGED if self._tag_calls else 0
     self._call_desc.flags |= self._obs_flags
     self._tag_host_count = self._tag_calls and not self._device_step_counter
-    self._dev_index = self._device.index
-    self._timesteps = None if self._scalar else [
-        dm_env.TimeStep(step_type=o['step_type'], reward=o['reward'], discount=o['discount'], observation=o['observation'])
-        for o in self._out]
     self._allocated = True
+
+  def _new_outputs(self, lead, place, observation=None):
+    """One set of output buffers: reward / discount f32 and step_type int8 of shape `lead` ((B,), or (T, B) for a
+    rollout), an observation tensor `lead + obs_shape` (or `observation`, ready-made), placed by the torch.empty
+    keywords `place` (device memory, or pinned host memory for the scalar view).  Returns the dict of tensors, the
+    TimeStepPtrs the library writes through and the TimeStep over the same tensors."""
+    o = dict(reward=torch.empty(lead, dtype=torch.float32, **place),
+             discount=torch.empty(lead, dtype=torch.float32, **place),
+             step_type=torch.empty(lead, dtype=torch.int8, **place),
+             observation=(observation if observation is not None else
+                          torch.empty(tuple(lead) + self._obs_shape, dtype=self._obs_dtype, **place)))
+    return o, _timestep_ptrs(o), dm_env.TimeStep(step_type=o['step_type'], reward=o['reward'], discount=o['discount'],
+                                                 observation=o['observation'])
+
+  def _sync_wrap(self):
+    """Writes the reward wrapper's tuple into the call descriptor (the wrappers install a NEW tuple when they change it:
+    `_call` tests identity against `_wrap_applied` instead of writing four fields per step)."""
+    w = self._call_desc.wrap
+    w.kind, w.param, w.seed, w.param2 = self._wrap
+    self._wrap_applied = self._wrap
+
+  def _redirected(self, method, *args):
+    """Kernels launch in the current device's context: a launching method of an environment that lives elsewhere
+    (several GPUs driven from one process) starts with
+        if _current_device() != self._dev_index: return self._redirected(self.<method>, *args)
+    which runs it again under the environment's own device."""
+    with torch.cuda.device(self._device):
+      return method(*args)
 
   # ----------------------------------------------------------------------------------------
   # the hot path
   def _call(self, action_ptr: int, force_reset: bool) -> int:
     """One reset()/step() launch; returns the index of the output buffer it wrote."""
     if _current_device() != self._dev_index:
-      # kernels launch in the current device's context: step an environment that lives elsewhere
-      # (several GPUs driven from one process) under its own device
-      with torch.cuda.device(self._device):
-        return self._call(action_ptr, force_reset)
+      return self._redirected(self._call, action_ptr, force_reset)
     b = self._buf
     self._buf = b + 1 if b + 1 < self._num_buffers else 0
     call = self._call_desc
@@ -491,7 +534,7 @@ class Environment(dm_env.EnvironmentBase):
       # current device IS this environment's here — the redirect at the top of _call — so this asks about the stream the
       # kernels are about to be launched on)
       call.flags = (0 if torch.cuda.is_current_stream_capturing() else _native.CALL_STATE_TAGGED) | self._obs_flags
-    if self._wrap is not self._wrap_applied:       # the wrappers install a NEW tuple when they change it
+    if self._wrap is not self._wrap_applied:       # (_sync_wrap, inline)
       w = self._call_wrap
       w.kind, w.param, w.seed, w.param2 = self._wrap
       self._wrap_applied = self._wrap
@@ -518,6 +561,32 @@ class Environment(dm_env.EnvironmentBase):
     self._step_index += 1
     return b
 
+  def _launch_steps(self, fn, args, T: int, what: str):
+    """The one launch path of the calls that make T steps at once (rollout, rollout_policy): `fn(*args)` with the call
+    descriptor — part of `args` — prepared as `_call` prepares it for one step, and the T call indices accounted for.
+    (`_call` keeps this protocol inline, for one step and pre-resolved arguments: tools/host_overhead.py.)"""
+    if _current_device() != self._dev_index:
+      return self._redirected(self._launch_steps, fn, args, T, what)
+    call = self._call_desc
+    call.force_reset, call.n_steps = 0, T
+    self._sync_wrap()
+    hip_stream = _current_raw_stream(self._dev_index)
+    call.hip_stream = hip_stream
+    # the call index of the first step: the host count, or 0 beside the device counter, which is then moved on by T
+    # unless its owner does that (shared_step_counter).  (Not aware of step_counter_deferred() blocks.)
+    call.stream.step_index = 0 if self._device_step_counter else self._step_index
+    try:
+      rc = fn(*args)
+      if rc == 0 and self._device_step_counter and self._shared_step_counter is None:
+        rc = _native.lib.bsx_counter_add(self._step_base.data_ptr(), T, hip_stream)
+    finally:
+      call.n_steps = 0
+      call.state_alt = None
+    if rc != 0:
+      _native.check(rc, f'{type(self).__name__} {what}')
+    self._step_index += T
+    return None
+
   # ----------------------------------------------------------------------------------------
   # batched `Logging` bookkeeping (bsuite/utils/wrappers.py:34-147), fused into the kernels
   def enable_logging(self, log_by_step: bool = False, log_every: bool = False,
@@ -535,7 +604,7 @@ class Environment(dm_env.EnvironmentBase):
     each row to its logger right after the step and reuses the buffer, so it never fills.  Rows past
     max_rows are counted, not stored, and `Logging.rows()` raises: pass max_rows / max_count for longer runs."""
     from bsuite_amd.utils import wrappers as _w  # pylint: disable=import-outside-toplevel
-    if getattr(self, '_grouped_by', None) is not None:
+    if self._grouped_by is not None:
       # (prepared groups hold this environment's column pointers — a pipelined pair of groups also a CLONE of the packed
       # state column, pending-miss bits of catch included — and the kernels they launch were chosen without Logging)
       raise RuntimeError('enable_logging() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
@@ -565,30 +634,22 @@ class Environment(dm_env.EnvironmentBase):
     # scalar view: the one lane's counters and rows sit in mapped host memory like its TimeStep, so
     # the Logging wrapper reads them after the step's synchronisation without device-to-host copies
     place = dict(pin_memory=True) if self._host_out else dict(device=dev)
-    lg = dict(
-        steps=torch.zeros(B, dtype=torch.int64, **place),
-        episode=torch.zeros(B, dtype=torch.int64, **place),
-        total_return=torch.zeros(B, dtype=torch.float64, **place),
-        episode_len=torch.zeros(B, dtype=torch.int64, **place),
-        episode_return=torch.zeros(B, dtype=torch.float64, **place),
-        rows=torch.zeros((B, max_rows, 5 + n_info), dtype=torch.float64, **place),
-        n_rows=torch.zeros(B, dtype=torch.int32, **place),
-        log_points=torch.tensor(points, dtype=torch.int64, device=dev))
+    lg = {k: torch.zeros(B, dtype=torch.float64 if k.endswith('_return') else torch.int64, **place)
+          for k in LOGGING_COLUMNS}
+    lg.update(rows=torch.zeros((B, max_rows, len(LOGGING_COLUMNS) + n_info), dtype=torch.float64, **place),
+              n_rows=torch.zeros(B, dtype=torch.int32, **place),
+              log_points=torch.tensor(points, dtype=torch.int64, device=dev))
     self._logging = lg
     self._logging_desc = _native.Logging(
-        steps=lg['steps'].data_ptr(), episode=lg['episode'].data_ptr(),
-        total_return=lg['total_return'].data_ptr(), episode_len=lg['episode_len'].data_ptr(),
-        episode_return=lg['episode_return'].data_ptr(), rows=lg['rows'].data_ptr(),
-        n_rows=lg['n_rows'].data_ptr(), info=self._info.data_ptr() if n_info else None,
-        log_points=lg['log_points'].data_ptr(), n_log_points=len(points), max_rows=max_rows,
+        info=self._info.data_ptr() if n_info else None, **{k: v.data_ptr() for k, v in lg.items()},
+        n_log_points=len(points), max_rows=max_rows,
         n_info=n_info, log_by_step=int(bool(log_by_step)), log_every=int(bool(log_every)))
-    import ctypes  # pylint: disable=import-outside-toplevel
     self._call_desc.logging = ctypes.pointer(self._logging_desc)
     return lg
 
   def logging_columns(self):
     """Column names of a snapshot row, in row order (STANDARD_KEYS first, wrappers.py:30-31)."""
-    return ('steps', 'episode', 'total_return', 'episode_len', 'episode_return') + tuple(self._info_keys)
+    return LOGGING_COLUMNS + tuple(self._info_keys)
 
   def _coerce_actions(self, action) -> torch.Tensor:
     if self._scalar:
@@ -673,7 +734,7 @@ class Environment(dm_env.EnvironmentBase):
     if self._scalar:
       raise ValueError('reset_mask / mark_reset() need the batched view (batch=B); reset() is the one lane of the '
                        'scalar view')
-    if getattr(self, '_grouped_by', None) is not None:
+    if self._grouped_by is not None:
       # (a pipelined pair of prepared groups holds a CLONE of the packed state column: a mark in this one would be lost)
       raise RuntimeError('mark_reset() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
     if (not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != self._device
@@ -683,8 +744,7 @@ class Environment(dm_env.EnvironmentBase):
 
   def _mark_reset(self, mask):
     if _current_device() != self._dev_index:
-      with torch.cuda.device(self._device):
-        return self._mark_reset(mask)
+      return self._redirected(self._mark_reset, mask)
     col = self._info_pending_column
     # `folded`: the info columns are maintained per episode (no Logging) — where _info_columns() decides it
     folded = 1 if (self._logging is None and col is not None) else 0
@@ -716,9 +776,6 @@ class Environment(dm_env.EnvironmentBase):
     overwritten by the next rollout of the same length."""
     if self._scalar:
       raise TypeError('rollout() needs the batched view (batch=B)')
-    if torch.cuda.is_available() and torch.cuda.current_device() != self._device.index:
-      with torch.cuda.device(self._device):
-        return self.rollout(actions)
     if self._delta:
       raise ValueError("rollout() writes T separate observation arrays; use observation_mode='dense'")
     self._ensure_allocated()
@@ -730,46 +787,18 @@ class Environment(dm_env.EnvironmentBase):
     T = int(actions.shape[0])
     if T < 1:
       raise ValueError('rollout needs at least one step')
-    cache = self.__dict__.setdefault('_rollout_out', {})
-    if T not in cache:
-      B, dev = self._batch, self._device
-      o = dict(reward=torch.empty((T, B), dtype=torch.float32, device=dev),
-               discount=torch.empty((T, B), dtype=torch.float32, device=dev),
-               step_type=torch.empty((T, B), dtype=torch.int8, device=dev),
-               observation=torch.empty((T, B) + self._obs_shape, dtype=self._obs_dtype, device=dev))
-      cache[T] = (o, _native.TimeStepPtrs(o['reward'].data_ptr(), o['discount'].data_ptr(),
-                                          o['step_type'].data_ptr(), o['observation'].data_ptr()))
-    out, ptrs = cache[T]
+    if T not in self._rollout_out:
+      self._rollout_out[T] = self._new_outputs((T, self._batch), dict(device=self._device))
+    _, ptrs, timestep = self._rollout_out[T]
     call = self._call_desc
-    call.force_reset = 0
-    call.n_steps = T
     if self._pipelined_rollout and T > 1 and not self._index:     # (no boards, no store stream to pipeline)
       # deep_sea / catch: a scratch state column lets every launch after the first carry the observation
       # stream of step t beside the lane advance of step t+1 (bsx_call_t.state_alt)
       if self._state_alt is None:
         self._state_alt = torch.empty_like(self._state['state'])
       call.state_alt = self._state_alt.data_ptr()
-    kind, param, wseed, param2 = self._wrap
-    call.wrap.kind, call.wrap.param, call.wrap.seed, call.wrap.param2 = kind, param, wseed, param2
-    self._wrap_applied = self._wrap
-    hip_stream = torch.cuda.current_stream(self._device).cuda_stream
-    call.hip_stream = hip_stream
-    try:
-      if self._device_step_counter:
-        rc = self._launch(call, actions.data_ptr(), ptrs)
-        if rc == 0 and self._shared_step_counter is None:
-          rc = _native.lib.bsx_counter_add(self._step_base.data_ptr(), T, hip_stream)
-      else:
-        call.stream.step_index = self._step_index
-        rc = self._launch(call, actions.data_ptr(), ptrs)
-    finally:
-      call.n_steps = 0
-      call.state_alt = None
-    if rc != 0:
-      _native.check(rc, f'{type(self).__name__} rollout')
-    self._step_index += T
-    return dm_env.TimeStep(step_type=out['step_type'], reward=out['reward'], discount=out['discount'],
-                           observation=out['observation'])
+    self._launch_steps(self._fn, self._native_args(call, actions.data_ptr(), ptrs), T, 'rollout')
+    return timestep
 
   _policy_abi = None   # subclass: the C-ABI entry point of rollout_policy (deep_sea, catch)
 
@@ -794,7 +823,7 @@ class Environment(dm_env.EnvironmentBase):
       raise ValueError('rollout_policy() is not available with Logging enabled')
     if self._wrap[0] != _native.WRAP_NONE:
       raise ValueError('rollout_policy() is not available under a reward wrapper')
-    if getattr(self, '_grouped_by', None) is not None:
+    if self._grouped_by is not None:
       raise RuntimeError('rollout_policy() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
     if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
       raise ValueError(f'rollout_policy: num_steps must be an integer >= 1, got {num_steps!r}')
@@ -836,50 +865,19 @@ class Environment(dm_env.EnvironmentBase):
     left as T step() calls leave them; calls interleave freely with step / rollout / mark_reset / reset.  Output buffers
     are cached per T and overwritten by the next call of the same T."""
     P = self._check_rollout_policy(policy, num_steps, policy_index, epsilon, explore_seed)
-    if torch.cuda.is_available() and torch.cuda.current_device() != self._device.index:
-      with torch.cuda.device(self._device):
-        return self.rollout_policy(policy, num_steps, policy_index=policy_index, epsilon=epsilon, explore_seed=explore_seed)
     self._ensure_allocated()
     T = int(num_steps)
-    cache = self.__dict__.setdefault('_policy_rollout_out', {})
-    if T not in cache:
-      B, dev = self._batch, self._device
-      o = dict(reward=torch.empty((T, B), dtype=torch.float32, device=dev),
-               discount=torch.empty((T, B), dtype=torch.float32, device=dev),
-               step_type=torch.empty((T, B), dtype=torch.int8, device=dev),
-               observation=torch.empty((T, B) + self._obs_shape, dtype=self._obs_dtype, device=dev),
-               actions=torch.empty((T, B), dtype=torch.int32, device=dev))
-      cache[T] = (o, _native.TimeStepPtrs(o['reward'].data_ptr(), o['discount'].data_ptr(),
-                                          o['step_type'].data_ptr(), o['observation'].data_ptr()))
-    out, ptrs = cache[T]
+    if T not in self._policy_rollout_out:
+      actions = torch.empty((T, self._batch), dtype=torch.int32, device=self._device)
+      self._policy_rollout_out[T] = self._new_outputs((T, self._batch), dict(device=self._device)) + (actions,)
+    _, ptrs, timestep, actions = self._policy_rollout_out[T]
     pol = _native.Policy(policy.data_ptr(), self.policy_num_states, P,
                          policy_index.data_ptr() if policy_index is not None else None,
-                         float(epsilon), int(explore_seed), out['actions'].data_ptr())
-    call = self._call_desc
-    call.force_reset = 0
-    call.n_steps = T
-    call.state_alt = None
-    hip_stream = torch.cuda.current_stream(self._device).cuda_stream
-    call.hip_stream = hip_stream
-    fn = getattr(_native.lib, self._policy_abi)
-    args = (ctypes.byref(self._cfg), ctypes.byref(call), ctypes.byref(pol), self._state['state'].data_ptr(), ptrs,
+                         float(epsilon), int(explore_seed), actions.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), ptrs,
             self._info.data_ptr())
-    try:
-      if self._device_step_counter:
-        call.stream.step_index = 0
-        rc = fn(*args)
-        if rc == 0 and self._shared_step_counter is None:
-          rc = _native.lib.bsx_counter_add(self._step_base.data_ptr(), T, hip_stream)
-      else:
-        call.stream.step_index = self._step_index
-        rc = fn(*args)
-    finally:
-      call.n_steps = 0
-    if rc != 0:
-      _native.check(rc, f'{type(self).__name__} rollout_policy')
-    self._step_index += T
-    return (dm_env.TimeStep(step_type=out['step_type'], reward=out['reward'], discount=out['discount'],
-                            observation=out['observation']), out['actions'])
+    self._launch_steps(getattr(_native.lib, self._policy_abi), args, T, 'rollout_policy')
+    return timestep, actions
 
   def _step(self, action):
     raise NotImplementedError('The batched engine fuses _step/_reset into one kernel; call step().')
@@ -973,14 +971,14 @@ class Environment(dm_env.EnvironmentBase):
     d['__step_index'] = self.device_step_index()
     d['__seed'] = self._seed
     if self._rng_mode == 'mt19937':
-      d['__mt_state'], d['__mt_pos'] = self._mt_state.clone(), self._mt_pos.clone()
-      d['__mt_gauss'], d['__mt_has_gauss'] = self._mt_gauss.clone(), self._mt_has_gauss.clone()
+      for k, v in self._mt.items():
+        d['__mt_' + k] = v.clone()
       if self._wrap_mt is not None:
         for k, v in self._wrap_mt.items():
           d['__wrap_mt_' + k] = v.clone()
     d['__wrap'] = tuple(self._wrap)                       # fused RewardNoise / RewardScale epilogue
     if self._logging is not None:                         # fused Logging bookkeeping (counters + rows)
-      for k in ('steps', 'episode', 'total_return', 'episode_len', 'episode_return', 'rows', 'n_rows'):
+      for k in LOGGING_COLUMNS + ('rows', 'n_rows'):
         d['__logging_' + k] = self._logging[k].clone()
     return d
 
@@ -1002,10 +1000,8 @@ class Environment(dm_env.EnvironmentBase):
     self._seed = int(d['__seed'])
     self._call_desc.stream.seed = self._seed
     if self._rng_mode == 'mt19937':
-      self._mt_state.copy_(d['__mt_state'])
-      self._mt_pos.copy_(d['__mt_pos'])
-      self._mt_gauss.copy_(d['__mt_gauss'])
-      self._mt_has_gauss.copy_(d['__mt_has_gauss'])
+      for k, v in self._mt.items():
+        v.copy_(d['__mt_' + k])
       if self._wrap_mt is not None:
         for k, v in self._wrap_mt.items():
           v.copy_(d['__wrap_mt_' + k])
@@ -1019,5 +1015,5 @@ class Environment(dm_env.EnvironmentBase):
     if has_log:
       if d['__logging_rows'].shape != self._logging['rows'].shape:
         raise ValueError('Logging row buffers differ in shape (max_rows): construct Logging with the same max_rows')
-      for k in ('steps', 'episode', 'total_return', 'episode_len', 'episode_return', 'rows', 'n_rows'):
+      for k in LOGGING_COLUMNS + ('rows', 'n_rows'):
         self._logging[k].copy_(d['__logging_' + k])

@@ -7,7 +7,6 @@ on the host once to find the first k whose sum exceeds `max_time` (the reference
 1001, not 1000, for the defaults) and to tabulate the f32 `time_elapsed / max_time` observation.
 """
 import collections
-import ctypes
 from typing import Optional
 
 import numpy as np
@@ -71,9 +70,6 @@ class _CartpoleBase(base.Environment):
                 steps=torch.full((self._batch,), 1 << 30, dtype=torch.int32, device=self._device))
 
   _abi_name = 'cartpole'
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), self._state['steps'].data_ptr(), out, self._info.data_ptr())
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

@@ -1,5 +1,4 @@
 """Batched Catch (counterpart of bsuite/environments/catch.py; kernel: csrc/catch.hip)."""
-import ctypes
 from typing import Optional
 
 import numpy as np
@@ -45,9 +44,6 @@ class Catch(base.Environment):
   _supports_narrow_obs = True
   _index_width = 2
   _pipelined_rollout = True
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())
 
   _policy_abi = 'bsx_catch_policy_rollout'
 

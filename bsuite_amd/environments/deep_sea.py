@@ -5,7 +5,6 @@ Same constructor arguments and semantics as `DeepSea` (deep_sea.py:51-101); the 
 bsuite_amd/csrc/deep_sea.hip.  The per-cell action mapping is drawn on the host with numpy's
 RandomState exactly as the reference does (:76-85) and shipped to the kernel as N*N bits.
 """
-import ctypes
 import warnings
 from typing import Optional
 
@@ -79,9 +78,6 @@ class DeepSea(base.Environment):
   # deterministic, un-wrapped step() is then ONE launch (deep_sea_step1_kernel) instead of lane advance + observation stream.
   _state_tag_bit = 1 << 18
   _state_lib_bits = 1 << 18
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())
 
   _policy_abi = 'bsx_deep_sea_policy_rollout'
 

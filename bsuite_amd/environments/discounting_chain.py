@@ -1,5 +1,4 @@
 """Batched DiscountingChain (counterpart of bsuite/environments/discounting_chain.py)."""
-import ctypes
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -38,9 +37,6 @@ class DiscountingChain(base.Environment):
     # count lanes outside -5..4 in invalid_action_count() instead of raising.
     if self._scalar_last_type == _native.FIRST:
       self._reward_timestep[action]  # pylint: disable=pointless-statement
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out)
 
   @property
   def optimal_return(self):

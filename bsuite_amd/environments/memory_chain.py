@@ -1,5 +1,4 @@
 """Batched MemoryChain (counterpart of bsuite/environments/memory_chain.py; kernel: csrc/memory_chain_env.h on the skeleton of csrc/small_obs.h)."""
-import ctypes
 from typing import Optional
 
 import torch
@@ -33,6 +32,3 @@ class MemoryChain(base.Environment):
                 context=torch.zeros(self._batch, dtype=torch.int64, device=self._device))
 
   _abi_name = 'memory_chain'
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), self._state['context'].data_ptr(), out, self._info.data_ptr())

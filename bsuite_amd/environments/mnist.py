@@ -1,5 +1,4 @@
 """Batched MNIST contextual bandit (counterpart of bsuite/environments/mnist.py; csrc/mnist.hip)."""
-import ctypes
 import warnings
 import weakref
 from typing import Optional
@@ -75,6 +74,3 @@ class MNISTBandit(base.Environment):
     return dict(state=torch.full((self._batch,), 1 << 28, dtype=torch.int32, device=self._device))
 
   _abi_name = 'mnist'
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())

@@ -1,5 +1,4 @@
 """Batched MountainCar (counterpart of bsuite/environments/mountain_car.py; kernel: csrc/mountain_car_env.h on the skeleton of csrc/small_obs.h)."""
-import ctypes
 from typing import Optional
 
 import torch
@@ -36,6 +35,3 @@ class MountainCar(base.Environment):
     steps = self._state['steps']
     running = (steps & (1 << 30)) == 0
     return {0: -torch.where(running, steps & 0x3FFFFFFF, torch.zeros_like(steps)).to(torch.float64)}
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), self._state['steps'].data_ptr(), out, self._info.data_ptr())

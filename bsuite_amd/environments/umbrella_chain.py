@@ -1,5 +1,4 @@
 """Batched UmbrellaChain (counterpart of bsuite/environments/umbrella_chain.py; kernel: csrc/umbrella_chain_env.h on the skeleton of csrc/small_obs.h)."""
-import ctypes
 from typing import Optional
 
 import torch
@@ -32,9 +31,6 @@ class UmbrellaChain(base.Environment):
     return dict(state=torch.full((self._batch,), 1 << 22, dtype=torch.int32, device=self._device))
 
   _abi_name = 'umbrella_chain'
-
-  def _native_args(self, call, action_ptr, out):
-    return (ctypes.byref(self._cfg), ctypes.byref(call), action_ptr, self._state['state'].data_ptr(), out, self._info.data_ptr())
 
   @property
   def optimal_return(self):

@@ -22,13 +22,17 @@ independent, so:
 Global lane ids are unique across the sweep (segment k starts where segment k-1 ended), so any
 assignment of segments to ranks reproduces the same per-lane trajectories.
 """
+import ctypes
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 import bsuite_amd
+from bsuite_amd import _native
+from bsuite_amd import distributed as bdist
 from bsuite_amd import sweep as _sweep
+from bsuite_amd.environments.base import raw as _raw
 
 
 def segment_table(bsuite_ids: Sequence[str], total_lanes: int) -> List[Tuple[str, int, int]]:
@@ -71,12 +75,43 @@ DEFAULT_SPLIT = True
 DEFAULT_ROWS_IN_STREAM = False
 
 
+def _obs_numel(env) -> int:
+  return int(np.prod(env.observation_spec().shape))
+
+
+def _two_kernel(raw) -> bool:
+  """A family whose step is a lane advance + an observation store stream (every other one: a small-observation family)."""
+  return raw._abi_name in ('deep_sea', 'catch', 'mnist')  # pylint: disable=protected-access
+
+
+def _in_store_stream(raw) -> bool:
+  """A segment with a share of its group's store stream: a two-kernel family — except catch boards small enough for
+  the lane advance to write them itself (fused tiles, csrc/catch.hip), which behave like a small-observation family."""
+  return _two_kernel(raw) and not (raw._abi_name == 'catch' and _obs_numel(raw) <= _native.FUSED_CATCH_MAX_CELLS)  # pylint: disable=protected-access
+
+
 class SweepBatch:
   """All (or some) bsuite_ids as lane segments on this rank's GPU."""
 
   def __init__(self, bsuite_ids: Optional[Sequence[str]] = None, total_lanes: int = 1 << 20, *,
                device=None, seed: int = 0, rank: int = 0, world_size: int = 1, num_streams: int = 32,
                env_kwargs: Optional[Dict[str, dict]] = None):
+    # what prepare_groups() sets up and release_groups() takes down (first: __del__ releases whatever a constructor that
+    # raised half-way has left)
+    self._groups = []
+    self._groups_by_cost = []
+    self._grouped_graph = None
+    self._pipe = None                          # step_grouped_streams(): the two HIP streams + their events
+    self._small = None
+    self._pending_steps = 0
+    self._pipelined = False
+    self._split = False
+    self._self_bump = False
+    self._state_alt = {}                       # pipelined: segment -> the clone of its packed state column
+    self._row_scratch = {}                     # rows_in_stream: (segment, parity) -> its row scratch (None: no row path)
+    self._group_outs = None
+    self._pipelined_outs = None
+    self.envs = []
     self.ids = list(_sweep.SWEEP if bsuite_ids is None else bsuite_ids)
     self.table = segment_table(self.ids, total_lanes)
     self.device = torch.device('cuda:0' if device is None else device)
@@ -97,7 +132,7 @@ class SweepBatch:
       probe.append(lanes * bytes_per_step(self._numel[-1]))
     self.rank_of = assign_segments(probe, world_size)
     self.local = [i for i, r in enumerate(self.rank_of) if r == rank]
-    self.envs, self.segments = [], []
+    self.segments = []
     # one device-resident call counter for the whole sweep: bumped once per sweep step
     self._step_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
     # One arena for every segment's observation buffer, in segment order, each on a 4 KiB boundary: the
@@ -124,12 +159,6 @@ class SweepBatch:
     self.num_streams = max(1, int(num_streams))
     self._graph = None
     self._streams = None
-    self._groups = []
-    self._groups_by_cost = []
-    self._grouped_graph = None
-    self._pipe = None                          # step_grouped_streams(): the two HIP streams + their events
-    self._small = None
-    self._pending_steps = 0
 
   def _alloc_obs(self, shape):
     n = int(np.prod(shape))
@@ -160,9 +189,8 @@ class SweepBatch:
     return out
 
   def _bump(self, grouped: bool = False):
-    if grouped and getattr(self, '_self_bump', False):
+    if grouped and self._self_bump:
       return                                 # BSX_FAM_SWEEP_MIXED: phase 0 bumps the counter when its last workgroup retires
-    from bsuite_amd import _native  # pylint: disable=import-outside-toplevel
     _native.check(_native.lib.bsx_counter_add(self._step_counter.data_ptr(), 1,
                                               torch.cuda.current_stream(self.device).cuda_stream),
                   'sweep step counter')
@@ -208,19 +236,15 @@ class SweepBatch:
     writes).  `step_grouped()` then returns the TimeSteps of the step whose stream it launched — the lanes
     (state, info, episode counters) are one advance ahead of them; `release_groups()` leaves the state in
     the environments' own columns."""
-    import ctypes  # pylint: disable=import-outside-toplevel
-    from bsuite_amd import _native  # pylint: disable=import-outside-toplevel
-    from bsuite_amd import dm_env_compat as dm_env  # pylint: disable=import-outside-toplevel
     self.release_groups()
     rows_in_stream = DEFAULT_ROWS_IN_STREAM if rows_in_stream is None else bool(rows_in_stream)
     torch.cuda.set_device(self.device)       # the argument tables are allocated on the current device
     buckets = {}
     for k, env in enumerate(self.envs):
-      raw = env.raw_env if hasattr(env, 'raw_env') else env
+      raw = _raw(env)
       raw._ensure_allocated()  # pylint: disable=protected-access
-      numel = int(np.prod(raw.observation_spec().shape))
-      small = raw._abi_name not in ('deep_sea', 'catch', 'mnist')  # pylint: disable=protected-access
-      klass = _native.lib.bsx_group_small_class(numel) if small else 0
+      small = not _two_kernel(raw)
+      klass = _native.lib.bsx_group_small_class(_obs_numel(raw)) if small else 0
       group_family = ('sweep_mixed' if mix_all else 'small_mixed' if (small and mix_small) else
                       'pair_mixed' if (not small and mix_pairs) else raw._abi_name)  # pylint: disable=protected-access
       if mix_all:
@@ -228,90 +252,82 @@ class SweepBatch:
       buckets.setdefault((group_family, klass), []).append(k)
     if pipelined and not mix_all:
       raise ValueError('pipelined sweep steps need the whole-sweep group (mix_all)')
-    outs = [None] * len(self.envs)
-    outs_of = [outs, [None] * len(self.envs)]
-    self._state_alt = {}
-    self._row_scratch = {}
+    outs_of = [[None] * len(self.envs), [None] * len(self.envs)]
+    self._state_alt, self._row_scratch = {}, {}
     costs = []
     for (name, _), members in sorted(buckets.items()):
       if name == 'sweep_mixed' and heavy_first:
-        # Phase 0 ends when its slowest workgroup retires: put the long-running ones — wide observation rows
-        # (umbrella_distract draws and writes up to 103 floats per lane) — at the front of the grid and the
-        # cheap lane-advance workgroups of the two-kernel families at its end.
-        def weight(k):
-          raw_k = self.envs[k].raw_env if hasattr(self.envs[k], 'raw_env') else self.envs[k]
-          numel_k = int(np.prod(raw_k.observation_spec().shape))
-          # (small catch boards are written by phase 0 itself, 200 bytes per lane: they belong with the heavy ones)
-          small_k = (raw_k._abi_name not in ('deep_sea', 'catch', 'mnist') or  # pylint: disable=protected-access
-                     (raw_k._abi_name == 'catch' and numel_k <= _native.FUSED_CATCH_MAX_CELLS))  # pylint: disable=protected-access
-          # (segments with a share of the phase-1 store stream — the two-kernel families, and the chains' wide rows when the
-          # stream writes them — are the tail of the group: what bsx_group_step_split launches first, on its own)
-          if small_k and rows_in_stream and raw_k._row_scratch_words():  # pylint: disable=protected-access
-            return 1
-          return -numel_k if small_k else 2
-        members = sorted(members, key=weight)
-      def build(parity):
-        handle = ctypes.c_void_p()
-        _native.check(_native.lib.bsx_group_create(_native.FAMILY_IDS[name], len(members), ctypes.byref(handle)),
-                      'bsx_group_create')
-        self._groups.append(handle)
-        for idx, k in enumerate(members):
-          raw = self.envs[k].raw_env if hasattr(self.envs[k], 'raw_env') else self.envs[k]
-          extra = {}
-          o = raw._out[0]  # pylint: disable=protected-access
-          if pipelined:
-            # (small catch boards are written by phase 0 itself — fused tiles, csrc/catch.hip — so in a pipelined pair
-            # of groups they behave like a small-observation family: one state column, an observation buffer per group)
-            pair = (raw._abi_name in ('deep_sea', 'mnist') or  # pylint: disable=protected-access
-                    (raw._abi_name == 'catch' and int(np.prod(raw.observation_spec().shape)) > _native.FUSED_CATCH_MAX_CELLS))  # pylint: disable=protected-access
-            if pair:
-              if k not in self._state_alt:
-                self._state_alt[k] = raw._state['state'].clone()  # pylint: disable=protected-access
-              extra = dict(state_alt=self._state_alt[k], swap_state=(parity == 1))
-          if name == 'sweep_mixed' and rows_in_stream:
-            # memory_chain / umbrella_chain with a wide row: phase 0 leaves the row packed in a scratch and the group's
-            # store stream writes the observation (csrc/row_stream.h); the groups of a pipelined pair bring one each
-            key = (k, parity)
-            if key not in self._row_scratch:
-              rs = raw._row_scratch(fresh=(parity == 1))  # pylint: disable=protected-access
-              self._row_scratch[key] = rs
-            if self._row_scratch[key] is not None:
-              extra['row_scratch'] = self._row_scratch[key]
-          elif name == 'sweep_mixed':
-            extra['row_scratch'] = False             # (A/B: not even the scratch a large segment steps with on its own)
-          if pipelined:
-            if parity == 1:
-              o = dict(reward=torch.empty_like(o['reward']), discount=torch.empty_like(o['discount']),
-                       step_type=torch.empty_like(o['step_type']),
-                       observation=o['observation'] if pair else torch.empty_like(o['observation']))
-              extra['out'] = o
-          _native.check(raw._group_set(handle, idx, actions[k], **extra), f'bsx_group_set_{raw._abi_name}')  # pylint: disable=protected-access
-          raw._grouped_by = self  # pylint: disable=protected-access  (enable_logging refuses until release_groups())
-          outs_of[parity][k] = dm_env.TimeStep(step_type=o['step_type'], reward=o['reward'], discount=o['discount'],
-                                               observation=o['observation'])
-        _native.check(_native.lib.bsx_group_commit(handle), 'bsx_group_commit')
-      build(0)
-      if pipelined:
-        build(1)
-      costs.append(sum(self.segments[k][2] * bytes_per_step(int(np.prod(self.envs[k].observation_spec().shape)))
-                       for k in members))
+        members = sorted(members, key=lambda k: self._segment_weight(k, rows_in_stream))
+      for parity in (0, 1) if pipelined else (0,):
+        self._build_group(name, members, parity, actions, pipelined, rows_in_stream, outs_of[parity])
+      costs.append(sum(self.segments[k][2] * bytes_per_step(_obs_numel(self.envs[k])) for k in members))
     order = sorted(range(len(costs)), key=lambda j: -costs[j])
     self._groups_by_cost = [self._groups[j] for j in order]     # heaviest store streams first
     self._self_bump = mix_all                 # a whole-sweep group moves the call counter on by itself
     self._group_actions = list(actions)      # keep the static action tensors alive
-    self._group_outs = outs
+    self._group_outs = outs_of[0]
     self._pipelined = bool(pipelined)
     # (the split cut needs the segments with a share of the store stream at the tail of the group: the heavy_first order)
     self._split = bool(DEFAULT_SPLIT if split is None else split) and mix_all and not pipelined and heavy_first
     self._pipelined_outs = outs_of
     self._pipelined_step = 0
-    return outs_of if pipelined else outs
+    return outs_of if pipelined else outs_of[0]
+
+  def _segment_weight(self, k: int, rows_in_stream: bool):
+    """Sort key of segment k inside the whole-sweep group.  Phase 0 ends when its slowest workgroup retires: the
+    long-running ones — wide observation rows (umbrella_distract draws and writes up to 103 floats per lane; small catch
+    boards, written by phase 0 itself, 200 bytes per lane, belong with them) — go to the front of the grid, widest first.
+    The segments with a share of the phase-1 store stream — the two-kernel families with their cheap lane-advance
+    workgroups, and before them the chains' wide rows when the stream writes them — are the tail of the group: what
+    bsx_group_step_split launches first, on its own."""
+    raw = _raw(self.envs[k])
+    if _in_store_stream(raw):
+      return 2
+    if rows_in_stream and raw._row_scratch_words():  # pylint: disable=protected-access
+      return 1
+    return -_obs_numel(raw)
+
+  def _build_group(self, name, members, parity, actions, pipelined, rows_in_stream, outs):
+    """Creates the group `name` over the segments `members`, records each with its static actions and commits the
+    argument table; `outs[k]` becomes the TimeStep the group writes for segment k.  parity 1 is the second group of a
+    pipelined pair: state columns swapped, buffers of its own."""
+    handle = ctypes.c_void_p()
+    _native.check(_native.lib.bsx_group_create(_native.FAMILY_IDS[name], len(members), ctypes.byref(handle)),
+                  'bsx_group_create')
+    self._groups.append(handle)
+    for idx, k in enumerate(members):
+      raw = _raw(self.envs[k])
+      extra = {}
+      outs[k] = raw._timesteps[0]  # pylint: disable=protected-access
+      # (in a pipelined pair of groups a segment outside the store stream has one state column and an observation
+      # buffer per group)
+      pair = pipelined and _in_store_stream(raw)
+      if pair:
+        if k not in self._state_alt:
+          self._state_alt[k] = raw._state['state'].clone()  # pylint: disable=protected-access
+        extra = dict(state_alt=self._state_alt[k], swap_state=(parity == 1))
+      if name == 'sweep_mixed' and rows_in_stream:
+        # memory_chain / umbrella_chain with a wide row: phase 0 leaves the row packed in a scratch and the group's
+        # store stream writes the observation (csrc/row_stream.h); the groups of a pipelined pair bring one each
+        key = (k, parity)
+        if key not in self._row_scratch:
+          self._row_scratch[key] = raw._row_scratch(fresh=(parity == 1))  # pylint: disable=protected-access
+        if self._row_scratch[key] is not None:
+          extra['row_scratch'] = self._row_scratch[key]
+      elif name == 'sweep_mixed':
+        extra['row_scratch'] = False             # (A/B: not even the scratch a large segment steps with on its own)
+      if pipelined and parity == 1:
+        own = raw._out[0]['observation']  # pylint: disable=protected-access
+        extra['out'], _, outs[k] = raw._new_outputs(  # pylint: disable=protected-access
+            (raw.batch_size,), dict(device=self.device), own if pair else None)
+      _native.check(raw._group_set(handle, idx, actions[k], **extra), f'bsx_group_set_{raw._abi_name}')  # pylint: disable=protected-access
+      raw._grouped_by = self  # pylint: disable=protected-access  (enable_logging refuses until release_groups())
+    _native.check(_native.lib.bsx_group_commit(handle), 'bsx_group_commit')
 
   def step_grouped(self):
     """One sweep step = one grouped launch per (family, class) + one call-counter bump."""
-    from bsuite_amd import _native  # pylint: disable=import-outside-toplevel
     stream = torch.cuda.current_stream(self.device).cuda_stream
-    if getattr(self, '_pipelined', False):
+    if self._pipelined:
       # one launch: observation stream of sweep step s (group s & 1) | lane advance of step s + 1 (the other)
       s = self._pipelined_step
       if s == 0:                               # prologue: the lane advance of step 0 on its own
@@ -323,7 +339,7 @@ class SweepBatch:
       self._pipelined_step = s + 1
       self._pending_steps += 1
       return self._pipelined_outs[s & 1]
-    step = _native.lib.bsx_group_step_split if getattr(self, '_split', False) else _native.lib.bsx_group_step
+    step = _native.lib.bsx_group_step_split if self._split else _native.lib.bsx_group_step
     for handle in self._groups:
       rc = step(handle, stream)
       if rc == _native.BSX_EMODE and step is _native.lib.bsx_group_step_split:
@@ -352,9 +368,8 @@ class SweepBatch:
     graph starts dependent nodes 6-14 us apart and consecutive replays ~20 us apart,
     profiles/r02/sweep_graph_timeline_*.txt.)  Call `join_streams()` before reading the outputs on
     the current stream."""
-    if getattr(self, '_pipelined', False):
+    if self._pipelined:
       raise RuntimeError('pipelined groups alternate inside step_grouped(); prepare_groups(pipelined=False) for this schedule')
-    from bsuite_amd import _native  # pylint: disable=import-outside-toplevel
     if self._pipe is None:
       cur = torch.cuda.current_stream(self.device)
       self._pairs = [h for h in self._groups_by_cost if _native.lib.bsx_group_phases(h) == 2]
@@ -414,8 +429,7 @@ class SweepBatch:
     n, self._pending_steps = self._pending_steps, 0
     if n:
       for env in self.envs:
-        raw = env.raw_env if hasattr(env, 'raw_env') else env
-        raw._step_index += n  # pylint: disable=protected-access
+        _raw(env)._step_index += n  # pylint: disable=protected-access
 
   def sync(self):
     """join_streams() + flush_step_indices() + a device synchronisation: call before inspecting the
@@ -445,9 +459,8 @@ class SweepBatch:
     phased=False: whole groups as `num_streams` round-robin branches (the r01 topology).
     Groups are independent (disjoint segments); the shared call counter is bumped after the join.
     Call prepare_groups() first; then `replay_grouped()` per sweep step."""
-    if getattr(self, '_pipelined', False):
+    if self._pipelined:
       raise RuntimeError('pipelined groups alternate inside step_grouped(); prepare_groups(pipelined=False) for this schedule')
-    from bsuite_amd import _native  # pylint: disable=import-outside-toplevel
     if not self._groups:
       raise RuntimeError('capture_grouped() needs prepare_groups() first')
     self.step_grouped()                        # one eager step: first-use work stays out of the capture
@@ -505,28 +518,24 @@ class SweepBatch:
     return self._group_outs
 
   def release_groups(self):
-    from bsuite_amd import _native  # pylint: disable=import-outside-toplevel
     self._grouped_graph = None
-    if hasattr(self, '_pending_steps'):
-      self.flush_step_indices()
-    if getattr(self, '_pipe', None) is not None:
+    self.flush_step_indices()
+    if self._pipe is not None:
       self.join_streams()
       torch.cuda.synchronize(self.device)
       self._pipe = self._small = None
-    if getattr(self, '_pipelined', False) and self._groups:
+    if self._pipelined and self._groups:
       # advances of odd steps wrote the alternate state columns: hand the lanes back in the environments' own
       if self._pipelined_step % 2 == 1:
         for k, alt in self._state_alt.items():
-          raw = self.envs[k].raw_env if hasattr(self.envs[k], 'raw_env') else self.envs[k]
-          raw._state['state'].copy_(alt)  # pylint: disable=protected-access
+          _raw(self.envs[k])._state['state'].copy_(alt)  # pylint: disable=protected-access
       torch.cuda.synchronize(self.device)
       self._pipelined, self._state_alt = False, {}
     for handle in self._groups:
       _native.lib.bsx_group_destroy(handle)
     if self._groups:
       for e in self.envs:
-        raw = e.raw_env if hasattr(e, 'raw_env') else e
-        raw._grouped_by = None  # pylint: disable=protected-access
+        _raw(e)._grouped_by = None  # pylint: disable=protected-access
     self._groups = []
     self._groups_by_cost = []
 
@@ -570,7 +579,6 @@ class SweepBatch:
 
   def summary(self) -> Dict[str, Dict[str, float]]:
     """Per local bsuite_id: lanes, episodes finished/started, sum of every bsuite_info column."""
-    from bsuite_amd import distributed as bdist  # pylint: disable=import-outside-toplevel
     self.join_streams()
     self.flush_step_indices()
     out = {}

@@ -35,11 +35,11 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     # `env` is an engine environment or another wrapper around one: the reference composes its wrappers
     # freely (utils/wrappers_test.py:123-131 stacks RewardNoise on RewardScale); here every reward
     # wrapper in the stack folds into the ONE fused epilogue of the raw environment's kernel.
-    raw = env.raw_env if hasattr(env, 'raw_env') else env
+    raw = base.raw(env)
     if not isinstance(raw, base.Environment):
       raise TypeError('bsuite_amd reward wrappers fuse into a bsuite_amd environment kernel; got '
                       f'{type(env).__name__}')
-    if getattr(raw, '_logging', None) is not None:
+    if raw._logging is not None:  # pylint: disable=protected-access
       # The fused Logging bookkeeping tracks the reward the kernel's epilogue returns, i.e. it always behaves as the
       # OUTERMOST wrapper.  In the reference a Logging *inside* a reward wrapper records the un-perturbed rewards
       # (utils/wrappers.py:74-77 sees the inner env's timestep): that composition would silently log other
@@ -87,10 +87,7 @@ class _RewardWrapper(dm_env.EnvironmentBase):
   @property
   def raw_env(self):
     # Recursively unwrap until we reach the true 'raw' env.
-    wrapped = self._env
-    if hasattr(wrapped, 'raw_env'):
-      return wrapped.raw_env
-    return wrapped
+    return base.raw(self._env)
 
   def bsuite_info(self) -> Dict[str, Any]:
     return self._env.bsuite_info()
@@ -154,7 +151,7 @@ class RewardScale(_RewardWrapper):
 
 
 # Keys that are present for all experiments (wrappers.py:30-31).
-STANDARD_KEYS = frozenset(['steps', 'episode', 'total_return', 'episode_len', 'episode_return'])
+STANDARD_KEYS = frozenset(base.LOGGING_COLUMNS)
 
 
 def _logarithmic_logging(episode: int, ratios: Optional[Sequence[float]] = None) -> bool:
@@ -190,7 +187,7 @@ class Logging(_RewardWrapper):
 
   def __init__(self, env, logger=None, log_by_step: bool = False, log_every: bool = False,
                max_rows: Optional[int] = None):
-    raw = env.raw_env if hasattr(env, 'raw_env') else env
+    raw = base.raw(env)
     super().__init__(raw)
     self._env = env
     self._raw = raw
@@ -296,7 +293,7 @@ class Logging(_RewardWrapper):
     tensor."""
     if check:
       self.check_overflow()
-    return {k: self._lg[k] for k in ('steps', 'episode', 'total_return', 'episode_len', 'episode_return')}
+    return {k: self._lg[k] for k in base.LOGGING_COLUMNS}
 
 
 # ---------------------------------------------------------------------------------------------

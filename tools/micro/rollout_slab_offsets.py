@@ -56,7 +56,7 @@ def run(bid, off):
     o, at = carve(pool, at, (T, B) + tuple(raw._obs_shape), torch.float32); at += off
     s, at = carve(pool, at, (T, B), torch.int8)
     out = dict(reward=r, discount=d, step_type=s, observation=o)
-    raw._rollout_out[T] = (out, _native.TimeStepPtrs(r.data_ptr(), d.data_ptr(), s.data_ptr(), o.data_ptr()))
+    raw._rollout_out[T] = (out, _native.TimeStepPtrs(r.data_ptr(), d.data_ptr(), s.data_ptr(), o.data_ptr()), None)  # (no TimeStep: timing only)
   for _ in range(4):
     env.rollout(acts)
   torch.cuda.synchronize()

@@ -46,7 +46,7 @@ def main():
 
   def install(o):
     env.__dict__['_rollout_out'] = {T: (o, _native.TimeStepPtrs(o['reward'].data_ptr(), o['discount'].data_ptr(),
-                                                                 o['step_type'].data_ptr(), o['observation'].data_ptr()))}
+                                                                 o['step_type'].data_ptr(), o['observation'].data_ptr()), None)}   # (no TimeStep: timing only)
 
   def drop():
     env.__dict__['_rollout_out'] = {}
