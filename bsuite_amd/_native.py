@@ -111,6 +111,11 @@ class Policy(ctypes.Structure):
               ('actions_out', ctypes.c_void_p)]
 
 
+class PolicyEvalPtrs(ctypes.Structure):
+  """bsx_policy_eval_t: the three output columns of bsx_<family>_policy_evaluate."""
+  _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p)]
+
+
 class BanditCfg(ctypes.Structure):
   _fields_ = [('num_actions', ctypes.c_int32), ('_pad', ctypes.c_int32),
               ('rewards', ctypes.c_double * BANDIT_MAX_ACTIONS)]
@@ -190,6 +195,10 @@ _SIGS = {
                                      TimeStepPtrs, _P], ctypes.c_int),
     'bsx_catch_policy_rollout': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
                                   TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_deep_sea_policy_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
+                                      PolicyEvalPtrs, _P], ctypes.c_int),
+    'bsx_catch_policy_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
+                                   PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_bandit_step': ([ctypes.POINTER(BanditCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                         ctypes.c_int),
     'bsx_memory_chain_step': ([ctypes.POINTER(MemoryChainCfg), ctypes.POINTER(Call), _P, _P, _P,

@@ -311,6 +311,71 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_policy_rollout_kernel(const typ
   bsx_pool_counts(a.ctl, n_last, n_first, s_cnt, block_id & (BSX_COUNTER_SHARDS - 1));
 }
 
+// evaluate_policy(T): the closed loop of bsx_policy_rollout_kernel — same key, table, draws, selection and advance, in the
+// same order — with every per-step store removed.  The lane's state word, its three f64 sums and its episode count stay
+// in registers for the whole call (bsx_eval_accumulate, bsx_policy.h); what the advance would add to the bsuite_info
+// columns is counted in registers too (Fam::advance_deferred).  After the loop the thread stores the state word, the
+// three outputs and the info columns' deltas: B * ~28 bytes per call instead of T * B * ~20, no store and no barrier
+// inside the step loop.  The body of bsx_tab_eval_kernel (misc.hip), which picks the family per launch.
+template <class Fam, class HotFn>
+__device__ __forceinline__ void bsx_tab_eval_body(const typename Fam::args& a, const int n_steps, const HotFn& fn,
+                                                  const bsx_policy_args& p, const bsx_policy_eval_t& out,
+                                                  typename Fam::shared& s_fam, unsigned int* s_cnt, uint8_t* s_tab) {
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  Fam::stage(a, s_fam);
+  const int S = p.n_states;
+  const bool in_lds = p.in_lds != 0;                                      // uniform
+  if (in_lds) {
+    for (int k = threadIdx.x; k < S; k += BSX_BLOCK) s_tab[k] = p.table[k];
+  }
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  const bool mine = i < a.ctl.n_lanes;
+  const uint64_t lane = a.ctl.lane_offset + (uint64_t)i;
+  const uint64_t step0 = bsx_step_of(a.ctl);
+  const bool explore = p.epsilon > 0.0;                                   // uniform
+  uint32_t n_last = 0, n_first = 0;
+  if (mine) {
+    int32_t st = a.state[i];
+    const uint8_t* __restrict__ tab = p.table;
+    if (p.policy_index != nullptr) tab += (int64_t)bsx_policy_clamp(p.policy_index[i], p.n_policies) * S;
+    bsx_eval_acc e = {0.0, 0.0, 0.0, 0};
+    typename Fam::deferred pend = {};
+#pragma unroll 1
+    for (int t = 0; t < n_steps; ++t) {
+      const uint64_t step = step0 + (uint64_t)t;
+      const int key = bsx_policy_clamp(fn.policy_key(st), S);
+      uint32_t entry;                    // (two loads kept apart, as in the rollout kernel: merged, the lookup is a flat_load)
+      if (in_lds) {
+        entry = s_tab[key];
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(entry));
+#endif
+      } else {
+        entry = tab[key];
+      }
+      uint32_t w0 = 0, w1 = 0, w2 = 0;
+      if (explore) {
+        const bsx_u32x4 w = bsx_policy_draws(p.explore_seed, lane, step);
+        w0 = w.v[0]; w1 = w.v[1]; w2 = w.v[2];
+      }
+      const int act = bsx_policy_select(entry, Fam::resets(st), p.epsilon, w0, w1, w2, p.num_actions);
+      int32_t nst; double reward;
+      const int type = Fam::advance_deferred(a, s_fam, i, lane, step, st, act, nst, reward, pend);
+      st = nst;
+      bsx_eval_accumulate(&e, type, reward);
+      n_first += type == BSX_FIRST ? 1u : 0u;
+    }
+    n_last = (uint32_t)e.n;
+    a.state[i] = st;
+    out.episodes[i] = e.n;
+    out.return_sum[i] = e.total;
+    out.episode_return_sum[i] = e.done;
+    Fam::commit_deferred(a, i, pend);
+  }
+  bsx_pool_counts(a.ctl, n_last, n_first, s_cnt, blockIdx.x);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Observation stream kernel: a pure store stream over the whole [B x cells] observation array,
 // decoupled from the lane-advance kernel.  Block b writes the K*4 KiB run of floats

@@ -129,10 +129,9 @@ static int bsx_group_launch_pair(bsx_group* g, int phase, hipStream_t st) {
 int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes, int32_t family, int32_t p0, int32_t p1,
                             bool rollout, hipStream_t st);
 
-// The refusals of bsx_<family>_policy_rollout that do not depend on the family, in the documented order (include/bsuite_amd.h):
-// modes, scalars, then — for a call with lanes — pointers.  `n_states`: the family's table length for this cfg.
-static inline int bsx_check_policy_call(const bsx_call_t* call, const bsx_policy_t* pol, int32_t n_states, const int32_t* state,
-                                        const bsx_timestep_t& out, const double* info) {
+// The refusals of bsx_<family>_policy_rollout / _policy_evaluate that do not depend on the family, in the documented order
+// (include/bsuite_amd.h): modes, then scalars.  `n_states`: the family's table length for this cfg.
+static inline int bsx_check_policy_scalars(const bsx_call_t* call, const bsx_policy_t* pol, int32_t n_states) {
   if (call == nullptr || pol == nullptr) return BSX_ENULL;
   if ((call->flags & (BSX_CALL_OBS_MASK | BSX_CALL_OBS_INDEX)) != BSX_CALL_OBS_INDEX) return BSX_EMODE;
   if (call->logging != nullptr || call->wrap.kind != BSX_WRAP_NONE || call->stream.mt_state != nullptr ||
@@ -142,7 +141,14 @@ static inline int bsx_check_policy_call(const bsx_call_t* call, const bsx_policy
   if (call->n_steps < 1 || call->n_lanes < 0 || call->n_lanes > ((int64_t)1 << 40)) return BSX_EINVAL;
   if (pol->n_states != n_states || pol->n_policies < 1) return BSX_EINVAL;
   if (!(pol->epsilon >= 0.0 && pol->epsilon <= 1.0)) return BSX_ERANGE;      // (NaN included)
-  if (call->n_lanes == 0) return 0;
+  return 0;
+}
+
+// ... then, for a call with lanes, the pointers of a policy rollout.
+static inline int bsx_check_policy_call(const bsx_call_t* call, const bsx_policy_t* pol, int32_t n_states, const int32_t* state,
+                                        const bsx_timestep_t& out, const double* info) {
+  const int rc = bsx_check_policy_scalars(call, pol, n_states);
+  if (rc != 0 || call->n_lanes == 0) return rc;
   if (pol->table == nullptr || pol->actions_out == nullptr || state == nullptr || info == nullptr ||
       out.reward == nullptr || out.discount == nullptr || out.step_type == nullptr || out.observation == nullptr)
     return BSX_ENULL;
@@ -151,12 +157,22 @@ static inline int bsx_check_policy_call(const bsx_call_t* call, const bsx_policy
   return 0;
 }
 
-// Launches bsx_policy_rollout_kernel: `a` from the family's make() (its action pointer is never read).
-template <class Fam, class HotFn>
-static int bsx_policy_rollout_call(const typename Fam::args& a, const bsx_call_t* call, const bsx_policy_t* pol,
-                                   uint32_t num_actions, bsx_timestep_t out, const HotFn& fn) {
-  const int64_t blocks = bsx_blocks_of(call->n_lanes);
-  if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
+// ... and those of a policy evaluation: no TimeStep buffers, actions_out is not looked at, three output columns.
+static inline int bsx_check_policy_eval_call(const bsx_call_t* call, const bsx_policy_t* pol, int32_t n_states,
+                                             const int32_t* state, const bsx_policy_eval_t& out, const double* info) {
+  const int rc = bsx_check_policy_scalars(call, pol, n_states);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  if (pol->table == nullptr || state == nullptr || info == nullptr || out.episodes == nullptr || out.return_sum == nullptr ||
+      out.episode_return_sum == nullptr)
+    return BSX_ENULL;
+  if (pol->n_policies > 1 && pol->policy_index == nullptr) return BSX_ENULL;
+  if (call->action_ring < 0) return BSX_EINVAL;                              // (what bsx_check_call refuses for a rollout)
+  if (bsx_blocks_of(call->n_lanes) > 0x7FFFFFFF) return BSX_EINVAL;
+  return 0;
+}
+
+// bsx_policy_args of a call (`actions_out` is the rollout's alone).
+static inline bsx_policy_args bsx_make_policy_args(const bsx_policy_t* pol, uint32_t num_actions) {
   bsx_policy_args p;
   p.table = pol->table;
   p.policy_index = pol->n_policies > 1 ? pol->policy_index : nullptr;
@@ -166,6 +182,16 @@ static int bsx_policy_rollout_call(const typename Fam::args& a, const bsx_call_t
   p.n_states = pol->n_states; p.n_policies = pol->n_policies;
   p.num_actions = num_actions;
   p.in_lds = (pol->n_policies == 1 && pol->n_states <= BSX_POLICY_LDS_BYTES) ? 1 : 0;
+  return p;
+}
+
+// Launches bsx_policy_rollout_kernel: `a` from the family's make() (its action pointer is never read).
+template <class Fam, class HotFn>
+static int bsx_policy_rollout_call(const typename Fam::args& a, const bsx_call_t* call, const bsx_policy_t* pol,
+                                   uint32_t num_actions, bsx_timestep_t out, const HotFn& fn) {
+  const int64_t blocks = bsx_blocks_of(call->n_lanes);
+  if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
+  const bsx_policy_args p = bsx_make_policy_args(pol, num_actions);
   bsx_policy_rollout_kernel<Fam, HotFn><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)call->hip_stream>>>(
       a, call->n_steps, reinterpret_cast<int32_t*>(out.observation), fn, p);
   return bsx_launch_status();

@@ -53,4 +53,14 @@ BSX_HD int32_t bsx_policy_select(uint32_t table_byte, int resets, double epsilon
   return (int32_t)table_byte;
 }
 
+// What bsx_<family>_policy_evaluate keeps of a lane's steps instead of writing them (evaluate_policy): the episodes that
+// ended inside the call, the sum of all rewards, and the sum of the returns of the episodes that ended — the running
+// episode's return so far is `acc`.  `reward` is the f64 reward of the lane advance, before any rounding to float32;
+// step types are dm_env's (FIRST 0, MID 1, LAST 2: a FIRST step carries no reward).  Sums in step order, plain IEEE adds.
+typedef struct { double acc, done, total; int32_t n; } bsx_eval_acc;
+BSX_HD void bsx_eval_accumulate(bsx_eval_acc* e, int step_type, double reward) {
+  if (step_type != 0) { e->acc += reward; e->total += reward; }
+  if (step_type == 2) { e->done += e->acc; e->acc = 0.0; e->n += 1; }
+}
+
 #endif  // BSX_POLICY_H_

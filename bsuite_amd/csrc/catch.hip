@@ -10,12 +10,22 @@
 //            rows*cols = 50 is not a multiple of 4, so a 16-byte chunk may straddle two lanes'
 //            boards (one division per chunk, spill-over elements patched from lane l+1's state).
 #include "bsx_pair_host.h"
+#include "bsx_tab_eval.h"
 #include "catch_fam.h"
 #include "pair_mixed.h"
 
 // The cfg's range check, the same for every entry point.
 static int catch_check_cfg(const bsx_catch_t* cfg) {
   return (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) ? BSX_ERANGE : 0;
+}
+
+// The kernel argument struct of a checked call.
+static void catch_fill(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out,
+                       double* info, catch_fam::args* a) {
+  a->ctl = bsx_make_ctl(call);
+  a->action = action; a->state = state; a->out = out; a->info = info;
+  a->rows = cfg->rows; a->columns = cfg->columns;
+  a->tile_cells_magic = 0; a->_pad = 0;
 }
 
 static int catch_make(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
@@ -25,10 +35,7 @@ static int catch_make(const bsx_catch_t* cfg, const bsx_call_t* call, const int3
   if (rc != 0) return rc;
   if ((rc = catch_check_cfg(cfg)) != 0) return rc;
   if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
-  a->ctl = bsx_make_ctl(call);
-  a->action = action; a->state = state; a->out = out; a->info = info;
-  a->rows = cfg->rows; a->columns = cfg->columns;
-  a->tile_cells_magic = 0; a->_pad = 0;
+  catch_fill(cfg, call, action, state, out, info, a);
   return 0;
 }
 
@@ -54,6 +61,17 @@ extern "C" int bsx_catch_policy_rollout(const bsx_catch_t* cfg, const bsx_call_t
   if (rc != 0) return rc;
   a.action = nullptr;
   return bsx_policy_rollout_call<catch_fam, catch_hot>(a, call, policy, 3u, out, catch_hot{cfg->rows, cfg->columns});
+}
+
+extern "C" int bsx_catch_policy_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy, int32_t* state,
+                                          bsx_policy_eval_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = catch_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_policy_eval_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_tab_eval_args e;
+  catch_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &e.fam.catch_);          // (no action column, no TimeStep)
+  return bsx_tab_eval_call(e, BSX_FAM_CATCH, call, policy, 3u, out);
 }
 
 extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catch_t* cfg, const bsx_call_t* call,

@@ -34,8 +34,9 @@ struct catch_fam {
   __device__ static __forceinline__ void stage(const args&, shared&) {}
 
   // LEAN: counter-based draws only (the MT19937-exact mode is compiled out); NOMT: the same for a call that is not
-  // lean otherwise (Logging / RewardNoise on the counter-based stream)
-  template <bool LEAN = false, bool NOMT = false>
+  // lean otherwise (Logging / RewardNoise on the counter-based stream); DEFER: the fold of 127 pending misses into the
+  // total_regret column is left to the caller (advance_deferred)
+  template <bool LEAN = false, bool NOMT = false, bool DEFER = false>
   __device__ static __forceinline__ int advance(const args& a, const shared&, int64_t i, uint64_t lane,
                                                 uint64_t step, int32_t st, int act, int32_t& nst,
                                                 double& reward) {
@@ -66,7 +67,10 @@ struct catch_fam {
         } else if (paddle_x != ball_x) {
           // (also tried: a fire-and-forget global_atomic_add_f64 per miss — 100k scattered 8-byte atomics per step cost
           // the L2 more than the round trip cost the wave: 45.0 -> 50.4 us at 2^20 lanes, profiles/r03/ab_info_atomics.log)
-          if (++pending == CATCH_PENDING_MAX) { a.info[i] += 2.0 * CATCH_PENDING_MAX; pending = 0; }
+          if (++pending == CATCH_PENDING_MAX) {
+            if (!DEFER) a.info[i] += 2.0 * CATCH_PENDING_MAX;
+            pending = 0;
+          }
         }
         type = BSX_LAST;
       } else {
@@ -84,6 +88,21 @@ struct catch_fam {
   }
   // does the lane reset on its next call (the test advance() makes, without force_reset)?
   __device__ static __forceinline__ bool resets(int32_t st) { return (st & CATCH_RESET_BIT) != 0; }
+
+  // The lean advance without a store inside it (the step loop of bsx_tab_eval_body): the folds of 127 pending misses are
+  // counted in a register and commit_deferred() adds them to the column after the loop.  The column holds even integers
+  // far below 2^53, so one add of folds * 254 leaves the bits the folds' own adds would.
+  struct deferred { uint32_t folds; };
+  __device__ static __forceinline__ int advance_deferred(const args& a, const shared& s, int64_t i, uint64_t lane, uint64_t step,
+                                                         int32_t st, int act, int32_t& nst, double& reward, deferred& d) {
+    const int type = advance<true, false, true>(a, s, i, lane, step, st, act, nst, reward);
+    const uint32_t was = ((uint32_t)st >> CATCH_PENDING_SHIFT) & 0x7Fu, is = ((uint32_t)nst >> CATCH_PENDING_SHIFT) & 0x7Fu;
+    d.folds += (type == BSX_LAST && was == CATCH_PENDING_MAX - 1 && is == 0u) ? 1u : 0u;
+    return type;
+  }
+  __device__ static __forceinline__ void commit_deferred(const args& a, int64_t i, const deferred& d) {
+    if (d.folds != 0u) a.info[i] += 2.0 * CATCH_PENDING_MAX * (double)d.folds;
+  }
 };
 
 struct catch_hot {

@@ -16,6 +16,7 @@
 // lanes, synchronise and then store (per-block 230 KB tiles, or flat 16 KiB runs with ping-pong
 // state) measured 5.1-5.5 TB/s against 6.2-6.4 TB/s for this pair (profiles/r01/ab_*.log).
 #include "bsx_pair_host.h"
+#include "bsx_tab_eval.h"
 #include "deep_sea_fam.h"
 #include "pair_mixed.h"
 
@@ -144,6 +145,16 @@ static int deep_sea_check_cfg(const bsx_deep_sea_t* cfg) {
   return (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) ? BSX_ERANGE : 0;
 }
 
+// The kernel argument struct of a checked call.
+static void deep_sea_fill(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
+                          bsx_timestep_t out, double* info, deep_sea_fam::args* a) {
+  a->ctl = bsx_make_ctl(call);
+  a->action = action; a->state = state; a->out = out; a->info = info;
+  a->move_cost = cfg->move_cost; a->inv_size = cfg->inv_size;
+  a->size = cfg->size; a->deterministic = cfg->deterministic;
+  for (int w = 0; w < DS_MAP_WORDS; ++w) a->mapping_bits[w] = cfg->mapping_bits[w];
+}
+
 // Validates one call's arguments and fills the kernel argument struct (shared by step and group).
 static int deep_sea_make(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action,
                          int32_t* state, bsx_timestep_t out, double* info, deep_sea_fam::args* a) {
@@ -154,11 +165,7 @@ static int deep_sea_make(const bsx_deep_sea_t* cfg, const bsx_call_t* call, cons
   if (call->stream.mt_state != nullptr && !cfg->deterministic && call->stream.mt_gauss == nullptr)
     return BSX_ENULL;                      // the stochastic variant draws randn: needs the gauss cache columns
   if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
-  a->ctl = bsx_make_ctl(call);
-  a->action = action; a->state = state; a->out = out; a->info = info;
-  a->move_cost = cfg->move_cost; a->inv_size = cfg->inv_size;
-  a->size = cfg->size; a->deterministic = cfg->deterministic;
-  for (int w = 0; w < DS_MAP_WORDS; ++w) a->mapping_bits[w] = cfg->mapping_bits[w];
+  deep_sea_fill(cfg, call, action, state, out, info, a);
   return 0;
 }
 
@@ -204,6 +211,17 @@ extern "C" int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_
   if (rc != 0) return rc;
   a.action = nullptr;
   return bsx_policy_rollout_call<deep_sea_fam, deep_sea_hot>(a, call, policy, 2u, out, deep_sea_hot{cfg->size});
+}
+
+extern "C" int bsx_deep_sea_policy_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                                             int32_t* state, bsx_policy_eval_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_policy_eval_call(call, policy, bsx_policy_states_deep_sea(cfg->size), state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_tab_eval_args e;
+  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &e.fam.deep_sea);     // (no action column, no TimeStep)
+  return bsx_tab_eval_call(e, BSX_FAM_DEEP_SEA, call, policy, 2u, out);
 }
 
 extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_deep_sea_t* cfg,

@@ -101,6 +101,27 @@ struct deep_sea_fam {
   }
   // does the lane reset on its next call (the test advance() makes, without force_reset)?
   __device__ static __forceinline__ bool resets(int32_t st) { return (st & DS_RESET_BIT) != 0; }
+
+  // The lean advance without a store inside it (the step loop of bsx_tab_eval_body): advance(commit = false), with what it
+  // would have added to the two bsuite_info columns counted in registers — `good`: a step right in the last column
+  // (:121-123), `bad`: an episode that ended with the bad bit set (:140-143) — and added by commit_deferred() after the
+  // loop.  The columns hold integers far below 2^53, so one add of the count leaves the bits the single adds would.
+  struct deferred { uint32_t bad, good; };
+  __device__ static __forceinline__ int advance_deferred(const args& a, const shared& s, int64_t i, uint64_t lane, uint64_t step,
+                                                         int32_t st, int act, int32_t& nst, double& reward, deferred& d) {
+    const int type = advance<true>(a, s, i, lane, step, st, act, nst, reward, /*commit=*/false);
+    if (type != BSX_FIRST) {
+      const int col = (st >> 8) & 0xFF, cell = (st & 0xFF) * a.size + col;
+      const int mapped = (int)((s.map[cell >> 5] >> (cell & 31)) & 1u);
+      d.good += (col == a.size - 1 && act == mapped) ? 1u : 0u;
+      d.bad += (type == BSX_LAST && ((nst >> 16) & 1) != 0) ? 1u : 0u;
+    }
+    return type;
+  }
+  __device__ static __forceinline__ void commit_deferred(const args& a, int64_t i, const deferred& d) {
+    if (d.bad != 0u) a.info[i] += (double)d.bad;
+    if (d.good != 0u) a.info[a.ctl.n_lanes + i] += (double)d.good;
+  }
 };
 
 // hot cell of a lane from its packed state (observation stream kernel)

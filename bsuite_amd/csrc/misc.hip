@@ -5,6 +5,7 @@
 #include "bsx_host.h"
 #include "bsx_lane_reset.h"
 #include "bsx_pair_host.h"
+#include "bsx_tab_eval.h"
 #include "pair_mixed.h"
 
 extern "C" int bsx_abi_version(void) { return BSX_ABI_VERSION; }
@@ -44,6 +45,28 @@ int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   bsx_index_decode_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(rows, state, n_lanes, family, p0, p1, rollout ? 1 : 0);
   return 0;
+}
+
+// evaluate_policy (bsx_<family>_policy_evaluate): ONE kernel for deep_sea and catch — the family is a uniform switch, as in
+// the two kernels around it, and each branch is bsx_tab_eval_body (bsx_pair_device.h) instantiated for its family.  The LDS
+// holds the shared table and both families' own staging (deep_sea's action mapping; catch has none).
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_tab_eval_kernel(const bsx_tab_eval_args a) {
+  __shared__ deep_sea_fam::shared s_deep_sea;
+  __shared__ catch_fam::shared s_catch;
+  __shared__ unsigned int s_cnt[2];
+  __shared__ uint8_t s_tab[BSX_POLICY_LDS_BYTES];
+  if (a.family == BSX_FAM_DEEP_SEA)
+    bsx_tab_eval_body<deep_sea_fam, deep_sea_hot>(a.fam.deep_sea, a.n_steps, deep_sea_hot{a.fam.deep_sea.size}, a.p, a.out,
+                                                  s_deep_sea, s_cnt, s_tab);
+  else
+    bsx_tab_eval_body<catch_fam, catch_hot>(a.fam.catch_, a.n_steps, catch_hot{a.fam.catch_.rows, a.fam.catch_.columns}, a.p,
+                                            a.out, s_catch, s_cnt, s_tab);
+}
+
+int bsx_launch_tab_eval(const bsx_tab_eval_args& a, hipStream_t st) {
+  const int64_t n_lanes = a.family == BSX_FAM_DEEP_SEA ? a.fam.deep_sea.ctl.n_lanes : a.fam.catch_.ctl.n_lanes;
+  bsx_tab_eval_kernel<<<dim3((unsigned)bsx_blocks_of(n_lanes)), dim3(BSX_BLOCK), 0, st>>>(a);
+  return bsx_launch_status();
 }
 
 extern "C" const char* bsx_strerror(int code) {
@@ -89,6 +112,7 @@ extern "C" int bsx_calib_fill(void* dst, int64_t n_bytes, int32_t nontemporal, v
 // (state in; state, TimeStep scalars and the row out).  One 16-byte load per thread, W 16-byte stores (to W regions n_bytes
 // apart), no loop, blocks in address order: the rate (R + W bytes per second) such a mix reaches on this box is the
 // ceiling for a kernel that mixes reads into its writes, as the fill rate is for a pure store stream.
+// W = 2 is the mix the project measures against (bench.py's COPY ceiling): its stores are unrolled.
 template <int W>
 __global__ void __launch_bounds__(BSX_BLOCK) calib_copy_kernel(const bsx_f4* __restrict__ src, bsx_f4* __restrict__ dst, int64_t n16) {
   const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
@@ -96,6 +120,17 @@ __global__ void __launch_bounds__(BSX_BLOCK) calib_copy_kernel(const bsx_f4* __r
     const bsx_f4 v = src[i];
 #pragma unroll
     for (int w = 0; w < W; ++w) dst[(int64_t)w * n16 + i] = v;
+  }
+}
+// ... and every other mix (one store or three per load) from ONE kernel whose store count is an argument: the same
+// addresses, the same bytes, a rolled loop.
+__global__ void __launch_bounds__(BSX_BLOCK) calib_copy_n_kernel(const bsx_f4* __restrict__ src, bsx_f4* __restrict__ dst, int64_t n16,
+                                                                 int n_writes) {
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  if (i < n16) {
+    const bsx_f4 v = src[i];
+#pragma unroll 1
+    for (int w = 0; w < n_writes; ++w) dst[(int64_t)w * n16 + i] = v;
   }
 }
 
@@ -109,9 +144,8 @@ extern "C" int bsx_calib_copy(void* dst, const void* src, int64_t n_bytes, int32
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   hipStream_t st = (hipStream_t)hip_stream;
   const dim3 g((unsigned)blocks), b(BSX_BLOCK);
-  if (writes_per_read == 1) calib_copy_kernel<1><<<g, b, 0, st>>>((const bsx_f4*)src, (bsx_f4*)dst, n16);
-  else if (writes_per_read == 2) calib_copy_kernel<2><<<g, b, 0, st>>>((const bsx_f4*)src, (bsx_f4*)dst, n16);
-  else calib_copy_kernel<3><<<g, b, 0, st>>>((const bsx_f4*)src, (bsx_f4*)dst, n16);
+  if (writes_per_read == 2) calib_copy_kernel<2><<<g, b, 0, st>>>((const bsx_f4*)src, (bsx_f4*)dst, n16);
+  else calib_copy_n_kernel<<<g, b, 0, st>>>((const bsx_f4*)src, (bsx_f4*)dst, n16, writes_per_read);
   return bsx_launch_status();
 }
 

@@ -22,6 +22,7 @@ for the reference's run loop, which holds `timestep` and `new_timestep`
 
 There is no CPU fallback: without a HIP device the first reset()/step() raises.
 """
+import collections
 import contextlib
 import ctypes
 import secrets
@@ -60,6 +61,10 @@ LOGGING_COLUMNS = ('steps', 'episode', 'total_return', 'episode_len', 'episode_r
 
 # The per-lane columns of np.random.RandomState's state (rng='mt19937'), in the order of bsx_stream_t / bsx_reward_wrap_t.
 _MT_COLUMNS = ('state', 'pos', 'gauss', 'has_gauss')
+
+
+# What evaluate_policy() returns: three device tensors [B] (int32, float64, float64).
+PolicyEvaluation = collections.namedtuple('PolicyEvaluation', ['episodes', 'return_sum', 'episode_return_sum'])
 
 
 def raw(env):
@@ -170,6 +175,7 @@ class Environment(dm_env.EnvironmentBase):
     self._grouped_by = None            # the SweepBatch whose prepared groups hold this environment's column pointers
     self._rollout_out = {}             # rollout() / rollout_policy(): output buffers per T (_new_outputs)
     self._policy_rollout_out = {}
+    self._policy_eval_out = None       # evaluate_policy(): the three [B] columns
     self._state_alt = None             # pipelined rollouts: the scratch state column (allocated on first use)
     self._row_buf = None               # the row scratch of _row_scratch() (allocated on first use)
     self._dev_index = self._device.index
@@ -807,41 +813,41 @@ class Environment(dm_env.EnvironmentBase):
     """Entries of one table of `rollout_policy` (deep_sea: N * N, catch: rows * columns * columns)."""
     raise ValueError(f'{type(self).__name__} has no tabular policy rollout (deep_sea and catch only)')
 
-  def _check_rollout_policy(self, policy, num_steps, policy_index, epsilon, explore_seed):
-    """The refusals of rollout_policy(): all of them before any GPU use, nothing allocated."""
+  def _check_rollout_policy(self, policy, num_steps, policy_index, epsilon, explore_seed, what='rollout_policy'):
+    """The refusals of rollout_policy() and evaluate_policy() (`what`): all of them before any GPU use, nothing allocated."""
     name = type(self).__name__
     if self._policy_abi is None:
       raise ValueError(f'{name} has no tabular policy rollout (deep_sea and catch only)')
     if self._scalar:
-      raise ValueError('rollout_policy() needs the batched view (batch=B)')
+      raise ValueError(f'{what}() needs the batched view (batch=B)')
     if not self._index:
-      raise ValueError(f"rollout_policy() looks its actions up by the index observation: build the environment with "
+      raise ValueError(f"{what}() looks its actions up by the index observation: build the environment with "
                        f"observation_mode='index' (this one is {self.observation_mode!r}, {self._obs_dtype})")
     if self._rng_mode != 'philox':
-      raise ValueError("rollout_policy() needs the counter-based draw stream (rng='philox')")
+      raise ValueError(f"{what}() needs the counter-based draw stream (rng='philox')")
     if self._logging is not None:
-      raise ValueError('rollout_policy() is not available with Logging enabled')
+      raise ValueError(f'{what}() is not available with Logging enabled')
     if self._wrap[0] != _native.WRAP_NONE:
-      raise ValueError('rollout_policy() is not available under a reward wrapper')
+      raise ValueError(f'{what}() is not available under a reward wrapper')
     if self._grouped_by is not None:
-      raise RuntimeError('rollout_policy() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
+      raise RuntimeError(f'{what}() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
     if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
-      raise ValueError(f'rollout_policy: num_steps must be an integer >= 1, got {num_steps!r}')
+      raise ValueError(f'{what}: num_steps must be an integer >= 1, got {num_steps!r}')
     if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
-      raise ValueError(f'rollout_policy: epsilon must be a number in [0, 1], got {epsilon!r}')
+      raise ValueError(f'{what}: epsilon must be a number in [0, 1], got {epsilon!r}')
     if isinstance(explore_seed, bool) or not isinstance(explore_seed, (int, np.integer)) or not 0 <= int(explore_seed) < (1 << 64):
-      raise ValueError(f'rollout_policy: explore_seed must be an integer in [0, 2^64), got {explore_seed!r}')
+      raise ValueError(f'{what}: explore_seed must be an integer in [0, 2^64), got {explore_seed!r}')
     S = self.policy_num_states
     if (not torch.is_tensor(policy) or policy.dtype != torch.uint8 or policy.device != self._device or policy.dim() not in (1, 2)
         or int(policy.shape[-1]) != S or policy.numel() == 0 or not policy.is_contiguous()):
-      raise ValueError(f'rollout_policy: policy must be a contiguous uint8 tensor of shape ({S},) or (P, {S}) on {self._device}')
+      raise ValueError(f'{what}: policy must be a contiguous uint8 tensor of shape ({S},) or (P, {S}) on {self._device}')
     P = 1 if policy.dim() == 1 else int(policy.shape[0])
     if P == 1:
       if policy_index is not None:
-        raise ValueError('rollout_policy: policy_index names the row of a population of tables; with one table it must be None')
+        raise ValueError(f'{what}: policy_index names the row of a population of tables; with one table it must be None')
     elif (not torch.is_tensor(policy_index) or policy_index.dtype != torch.int32 or policy_index.device != self._device
           or tuple(policy_index.shape) != (self._batch,) or not policy_index.is_contiguous()):
-      raise ValueError(f'rollout_policy: a population of {P} tables needs policy_index, a contiguous int32 tensor of shape '
+      raise ValueError(f'{what}: a population of {P} tables needs policy_index, a contiguous int32 tensor of shape '
                        f'({self._batch},) on {self._device}')
     return P
 
@@ -878,6 +884,45 @@ class Environment(dm_env.EnvironmentBase):
             self._info.data_ptr())
     self._launch_steps(getattr(_native.lib, self._policy_abi), args, T, 'rollout_policy')
     return timestep, actions
+
+  _policy_eval_abi = None   # subclass: the C-ABI entry point of evaluate_policy (deep_sea, catch)
+
+  def evaluate_policy(self, policy, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`rollout_policy` with the same arguments, returns only: the lanes take the same `num_steps` steps in ONE launch — same
+    actions, draws, keys and clamps — and state, bsuite_info(), episode_counters(), invalid_action_count() and the call
+    index are left bit for bit where rollout_policy leaves them, but no TimeStep is written.  Returns a `PolicyEvaluation`
+    of three device tensors [B], per lane over the steps of this call in order, in float64:
+
+        acc = done = total = 0.0; n = 0
+        for t in range(T):                      # type_t, r_t: step type and reward of step t
+          if type_t != FIRST: acc += r_t; total += r_t
+          if type_t == LAST:  done += acc; acc = 0.0; n += 1
+        episodes = n (int32); return_sum = total; episode_return_sum = done
+
+    r_t is the float64 reward of the step BEFORE the rounding to float32 that a TimeStep's reward gets: return_sum is what
+    the reference's run loop sums from `timestep.reward` as Python floats (for deep_sea it differs from the sum of
+    rollout_policy's float32 rewards).  The mean episode return of a lane is episode_return_sum / episodes.  An episode
+    that is already running when the call starts contributes only the rewards of this call to episode_return_sum; after
+    mark_reset() of all lanes, reset() or on a fresh environment there is none.  Nothing is reduced over lanes on the
+    device (float64 atomics have no fixed order): to score a population, reduce on the lanes grouped by policy, e.g.
+    `torch.zeros(P, dtype=torch.float64, device=...).index_add_(0, policy_index.long(), ev.episode_return_sum)`.  The three
+    buffers are cached per environment and overwritten by the next call.  Calls interleave freely with step / rollout /
+    rollout_policy / mark_reset / reset."""
+    P = self._check_rollout_policy(policy, num_steps, policy_index, epsilon, explore_seed, what='evaluate_policy')
+    self._ensure_allocated()
+    if self._policy_eval_out is None:
+      self._policy_eval_out = PolicyEvaluation(
+          episodes=torch.empty(self._batch, dtype=torch.int32, device=self._device),
+          return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
+          episode_return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device))
+    ev = self._policy_eval_out
+    pol = _native.Policy(policy.data_ptr(), self.policy_num_states, P,
+                         policy_index.data_ptr() if policy_index is not None else None, float(epsilon), int(explore_seed), None)
+    out = _native.PolicyEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), out,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._policy_eval_abi), args, int(num_steps), 'evaluate_policy')
+    return ev
 
   def _step(self, action):
     raise NotImplementedError('The batched engine fuses _step/_reset into one kernel; call step().')

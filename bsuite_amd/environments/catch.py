@@ -46,6 +46,7 @@ class Catch(base.Environment):
   _pipelined_rollout = True
 
   _policy_abi = 'bsx_catch_policy_rollout'
+  _policy_eval_abi = 'bsx_catch_policy_evaluate'
 
   @property
   def policy_num_states(self) -> int:

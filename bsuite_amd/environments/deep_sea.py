@@ -80,6 +80,7 @@ class DeepSea(base.Environment):
   _state_lib_bits = 1 << 18
 
   _policy_abi = 'bsx_deep_sea_policy_rollout'
+  _policy_eval_abi = 'bsx_deep_sea_policy_evaluate'
 
   @property
   def policy_num_states(self) -> int:

@@ -72,6 +72,12 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'rollout_policy() is not available through {type(self).__name__}: the fused policy rollout has no '
                      'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
 
+  def evaluate_policy(self, policy, num_steps, **kwargs):
+    """Refused, like rollout_policy: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_policy)."""
+    del policy, num_steps, kwargs
+    raise ValueError(f'evaluate_policy() is not available through {type(self).__name__}: the fused policy evaluation has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -486,6 +492,12 @@ class ImageObservation(dm_env.EnvironmentBase):
     del policy, num_steps, kwargs
     raise ValueError('rollout_policy() is not available through ImageObservation: the fused policy rollout returns index '
                      'observations; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_policy(self, policy, num_steps, **kwargs):
+    """Refused, like rollout_policy: the fused evaluation looks actions up by index observations (base.Environment.evaluate_policy)."""
+    del policy, num_steps, kwargs
+    raise ValueError('evaluate_policy() is not available through ImageObservation: the fused policy evaluation looks its '
+                     'actions up by index observations; call it on an un-wrapped DeepSea / Catch')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

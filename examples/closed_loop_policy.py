@@ -2,7 +2,7 @@
 reads the observation tensor the engine just wrote — no host round trip anywhere in the loop.
 
     python examples/closed_loop_policy.py [bsuite_id] [lanes] [steps] [--observation-dtype float32|uint8|float16|bfloat16]
-                                          [--observation-mode dense|index] [--fused-table]
+                                          [--observation-mode dense|index] [--fused-table [--evaluate]]
 
 With a narrow --observation-dtype (deep_sea, catch) the engine writes the boards as bytes or 16-bit floats, and the policy
 converts each board once, as it reads it: to float32 from uint8, not at all from float16 / bfloat16, whose weights and
@@ -16,7 +16,9 @@ for the same weights, without the board ever being written or read.
 With --fused-table (deep_sea, catch; implies --observation-mode index) the same greedy policy is tabulated once — entry k
 of a uint8 table is the argmax of the logits of the observation with key k (`observations.policy_key`) — and the whole
 loop runs inside the engine: `env.rollout_policy(table, T)` is ONE launch for T closed-loop steps, and gives the same
-trajectories (the same bsuite_info sums) as the eager index run.
+trajectories (the same bsuite_info sums) as the eager index run.  With --evaluate on top the calls are
+`env.evaluate_policy(table, T)`: the same steps, but no TimeStep is written — three numbers per lane come back (episodes
+ended, sum of rewards, sum of the returns of the episodes that ended), and the mean episode return is printed from them.
 
 This is the batched counterpart of the reference run loop (bsuite/baselines/experiment.py:43-57):
 `timestep = env.step(agent.select_action(timestep))`, with 2^20 environments per call.
@@ -42,7 +44,10 @@ def main():
   ap.add_argument('--observation-dtype', default='float32', choices=('float32', 'uint8', 'float16', 'bfloat16'))
   ap.add_argument('--observation-mode', default='dense', choices=('dense', 'index'))
   ap.add_argument('--fused-table', action='store_true', help='tabulate the greedy policy and run the loop inside the engine (rollout_policy)')
+  ap.add_argument('--evaluate', action='store_true', help='with --fused-table: evaluate_policy instead of rollout_policy (returns only)')
   a = ap.parse_args()
+  if a.evaluate and not a.fused_table:
+    ap.error('--evaluate needs --fused-table')
   if a.fused_table:
     a.observation_mode = 'index'
   bsuite_id, lanes, steps = a.bsuite_id, a.lanes, a.steps
@@ -81,11 +86,18 @@ def main():
   ts = env.reset()
   if a.fused_table:
     fused = greedy_table()
-    env.rollout_policy(fused, 20)
+    run = env.evaluate_policy if a.evaluate else env.rollout_policy
+    run(fused, 20)
     torch.cuda.synchronize()
+    episodes = torch.zeros(lanes, dtype=torch.int64, device=fused.device)
+    returns = torch.zeros(lanes, dtype=torch.float64, device=fused.device)
     t0 = time.perf_counter()
     for n in [32] * (steps // 32) + ([steps % 32] if steps % 32 else []):
-      env.rollout_policy(fused, n)
+      ev = run(fused, n)
+      if a.evaluate:                              # (the three columns are overwritten by the next call)
+        episodes += ev.episodes
+        returns += ev.return_sum                  # (episode_return_sum counts only a call's own rewards of an episode the
+                                                  # calls cut in two; over many calls the sum of all rewards loses nothing)
   else:
     for _ in range(20):
       ts = env.step(policy(ts))
@@ -96,6 +108,8 @@ def main():
   torch.cuda.synchronize()
   dt = time.perf_counter() - t0
   info = {k: float(v.sum()) for k, v in env.bsuite_info().items()}
+  if a.evaluate:
+    print(json.dumps(dict(episodes=int(episodes.sum()), mean_episode_return=float(returns.sum() / episodes.sum().clamp(min=1)))))
   print(json.dumps(dict(bsuite_id=bsuite_id, observation_dtype=a.observation_dtype, observation_mode=a.observation_mode, fused_table=a.fused_table, lanes=lanes, steps=steps, ms_per_step=round(dt / steps * 1e3, 4),
                         env_steps_per_s=round(lanes * steps / dt), episodes_finished=int(env.episode_counters()[0]),
                         bsuite_info_sums=info)))

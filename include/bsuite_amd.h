@@ -324,6 +324,26 @@ int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* cal
 int bsx_catch_policy_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
                              int32_t* state, bsx_timestep_t out, double* info);
 
+/* ---- policy evaluation: the same closed loop, returns only (deep_sea, catch; v12, additive) ------
+ * bsx_<family>_policy_rollout without its outputs: the lanes take the same n_steps steps — same actions, draws, keys and
+ * clamps — and state, info, counters and the call index end up bit for bit as the rollout leaves them, but no TimeStep is
+ * written.  Per lane i, over the steps of the call in order (type_t, r_t: the step type and the f64 reward of step t,
+ * BEFORE the rounding to float32 a TimeStep's reward column gets):
+ *     acc = done = total = 0.0; n = 0
+ *     if type_t != BSX_FIRST: acc += r_t; total += r_t
+ *     if type_t == BSX_LAST:  done += acc; acc = 0.0; n += 1
+ *     episodes[i] = n; return_sum[i] = total; episode_return_sum[i] = done
+ * An episode already running when the call starts contributes only the rewards of this call to episode_return_sum.
+ * `call` is as for bsx_<family>_policy_rollout; policy->actions_out is not looked at and may be NULL; there are no
+ * TimeStep buffers.  Error codes and their order are the rollout's, with BSX_ENULL for a null output column.
+ * n_lanes == 0 returns 0 and launches nothing.  Asynchronous on call->hip_stream, no allocation, no synchronisation,
+ * graph-capturable. */
+typedef struct { int32_t* episodes; double* return_sum; double* episode_return_sum; } bsx_policy_eval_t;  /* device [n_lanes] each */
+int bsx_deep_sea_policy_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                                 int32_t* state, bsx_policy_eval_t out, double* info);
+int bsx_catch_policy_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                              int32_t* state, bsx_policy_eval_t out, double* info);
+
 /* ---- bandit : bsuite/environments/bandit.py:35-73 ----------------------------------------- */
 #define BSX_BANDIT_MAX_ACTIONS 32
 typedef struct {
