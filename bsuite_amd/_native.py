@@ -116,6 +116,18 @@ class PolicyEvalPtrs(ctypes.Structure):
   _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p)]
 
 
+class Linear(ctypes.Structure):
+  """bsx_linear_t: the linear policy of bsx_<family>_linear_evaluate."""
+  _fields_ = [('weights', ctypes.c_void_p), ('n_policies', ctypes.c_int32), ('policy_index', ctypes.c_void_p),
+              ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64), ('observation_in', ctypes.c_void_p)]
+
+
+class LinearEvalPtrs(ctypes.Structure):
+  """bsx_linear_eval_t: the three output columns and the final observation rows of bsx_<family>_linear_evaluate."""
+  _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p),
+              ('observation_out', ctypes.c_void_p)]
+
+
 class BanditCfg(ctypes.Structure):
   _fields_ = [('num_actions', ctypes.c_int32), ('_pad', ctypes.c_int32),
               ('rewards', ctypes.c_double * BANDIT_MAX_ACTIONS)]
@@ -209,10 +221,14 @@ _SIGS = {
                                     TimeStepPtrs], ctypes.c_int),
     'bsx_cartpole_step': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), _P, _P, _P,
                            TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_cartpole_linear_evaluate': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), ctypes.POINTER(Linear), _P, _P,
+                                      LinearEvalPtrs, _P], ctypes.c_int),
     'bsx_mnist_step': ([ctypes.POINTER(MnistCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                        ctypes.c_int),
     'bsx_mountain_car_step': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), _P, _P, _P,
                                TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_mountain_car_linear_evaluate': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), ctypes.POINTER(Linear), _P, _P,
+                                          LinearEvalPtrs, _P], ctypes.c_int),
 }
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({

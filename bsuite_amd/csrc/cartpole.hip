@@ -3,17 +3,11 @@
 // template instantiations, and compiling them side by side is what keeps a clean build() under a minute (round 6; as ONE
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
+#include "bsx_linear_score.h"
 #include "cartpole_env.h"
 
-static int cartpole_make(const bsx_cartpole_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, cartpole_env::args* a) {
-  if (cfg == nullptr) return BSX_ENULL;
-  int rc = bsx_check_call(call, action, out);
-  if (rc != 0) return rc;
-  if (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) return BSX_ERANGE;
-  if (call->n_lanes > 0 && (state == nullptr || steps == nullptr || info == nullptr || cfg->time_frac == nullptr))
-    return BSX_ENULL;
-  a->ctl = bsx_make_ctl(call); a->action = action; a->state = state; a->steps = steps; a->out = out;
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+// The parameters derived from a cfg on the host in f64, rounded once; BSX_ERANGE for a cfg outside the family's range.
+static int cartpole_derive(const bsx_cartpole_t* cfg, cartpole_env::args* a) {
   const double m_total = (double)cfg->mass_cart + (double)cfg->mass_pole;
   const double pole_ml = (double)cfg->mass_pole * (double)cfg->length;
   if (!(m_total > 0.0) || !(cfg->x_threshold > 0.0f) || !(cfg->length > 0.0f)) return BSX_ERANGE;
@@ -29,12 +23,37 @@ static int cartpole_make(const bsx_cartpole_t* cfg, const bsx_call_t* call, cons
   return 0;
 }
 
+static int cartpole_make(const bsx_cartpole_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, cartpole_env::args* a) {
+  if (cfg == nullptr) return BSX_ENULL;
+  int rc = bsx_check_call(call, action, out);
+  if (rc != 0) return rc;
+  if (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) return BSX_ERANGE;
+  if (call->n_lanes > 0 && (state == nullptr || steps == nullptr || info == nullptr || cfg->time_frac == nullptr))
+    return BSX_ENULL;
+  a->ctl = bsx_make_ctl(call); a->action = action; a->state = state; a->steps = steps; a->out = out;
+  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+  return cartpole_derive(cfg, a);
+}
+
 extern "C" int bsx_cartpole_step(const bsx_cartpole_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info) {
   cartpole_env::args a;
   int rc = cartpole_make(cfg, call, action, state, steps, out, info, &a);
   if (rc != 0) return rc;
   if (call->n_lanes == 0) return 0;
   return launch_small_obs<cartpole_env>(a, bsx_n_steps(call), call->hip_stream);
+}
+
+extern "C" int bsx_cartpole_linear_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear, float* state,
+                                             int32_t* steps, bsx_linear_eval_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || linear == nullptr) return BSX_ENULL;
+  bsx_linear_score_args e;
+  cartpole_env::args* a = &e.fam.cartpole;
+  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
+  if (rc == 0) rc = bsx_check_linear_call(call, linear, state, steps, out, info, cfg->time_frac);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
+  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+  return bsx_linear_score_call(e, BSX_FAM_CARTPOLE, call, linear, out);
 }
 
 extern "C" int bsx_group_set_cartpole(bsx_group_t* g, int32_t index, const bsx_cartpole_t* cfg, const bsx_call_t* call,

@@ -87,12 +87,16 @@ extern "C" const char* bsx_strerror(int code) {
 // boxes where a 4-stores-per-thread grid-stride fill reaches 5.8-6.0; profiles/r01/
 // store_calibration4_noloop.log).  What this reaches is the practical ceiling for a dense
 // observation stream on the box it runs on.
+// (NT = false is the only instantiation: the non-temporal fill, which nothing in the project measures against, is a mode of
+// calib_copy_n_kernel below — a kernel that can hardly ever launch still counts against the library's kernel budget.)
 template <bool NT>
 __global__ void __launch_bounds__(BSX_BLOCK) calib_fill_kernel(bsx_f4* __restrict__ p, int64_t n16) {
   const bsx_f4 z = {0.f, 0.f, 0.f, 0.f};
   const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
   if (i < n16) { if (NT) __builtin_nontemporal_store(z, &p[i]); else p[i] = z; }
 }
+
+__global__ void calib_copy_n_kernel(const bsx_f4* __restrict__ src, bsx_f4* __restrict__ dst, int64_t n16, int n_writes);
 
 extern "C" int bsx_calib_fill(void* dst, int64_t n_bytes, int32_t nontemporal, void* hip_stream) {
   if (dst == nullptr) return BSX_ENULL;
@@ -103,7 +107,7 @@ extern "C" int bsx_calib_fill(void* dst, int64_t n_bytes, int32_t nontemporal, v
   const int64_t blocks = bsx_blocks_of(n16);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
   hipStream_t st = (hipStream_t)hip_stream;
-  if (nontemporal) calib_fill_kernel<true><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>((bsx_f4*)dst, n16);
+  if (nontemporal) calib_copy_n_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(nullptr, (bsx_f4*)dst, n16, 0);
   else calib_fill_kernel<false><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>((bsx_f4*)dst, n16);
   return bsx_launch_status();
 }
@@ -123,10 +127,16 @@ __global__ void __launch_bounds__(BSX_BLOCK) calib_copy_kernel(const bsx_f4* __r
   }
 }
 // ... and every other mix (one store or three per load) from ONE kernel whose store count is an argument: the same
-// addresses, the same bytes, a rolled loop.
+// addresses, the same bytes, a rolled loop.  n_writes == 0 is bsx_calib_fill's non-temporal mode: nothing is read and the
+// thread's one 16-byte store of zeros is non-temporal — the shape of calib_fill_kernel.
 __global__ void __launch_bounds__(BSX_BLOCK) calib_copy_n_kernel(const bsx_f4* __restrict__ src, bsx_f4* __restrict__ dst, int64_t n16,
                                                                  int n_writes) {
   const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  if (n_writes == 0) {                                                    // uniform
+    const bsx_f4 z = {0.f, 0.f, 0.f, 0.f};
+    if (i < n16) __builtin_nontemporal_store(z, &dst[i]);
+    return;
+  }
   if (i < n16) {
     const bsx_f4 v = src[i];
 #pragma unroll 1

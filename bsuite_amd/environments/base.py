@@ -65,6 +65,8 @@ _MT_COLUMNS = ('state', 'pos', 'gauss', 'has_gauss')
 
 # What evaluate_policy() returns: three device tensors [B] (int32, float64, float64).
 PolicyEvaluation = collections.namedtuple('PolicyEvaluation', ['episodes', 'return_sum', 'episode_return_sum'])
+# What evaluate_linear() returns: the same three columns and the observation of the call's last step, float32 [B, *obs_shape].
+LinearEvaluation = collections.namedtuple('LinearEvaluation', ['episodes', 'return_sum', 'episode_return_sum', 'observation'])
 
 
 def raw(env):
@@ -176,6 +178,7 @@ class Environment(dm_env.EnvironmentBase):
     self._rollout_out = {}             # rollout() / rollout_policy(): output buffers per T (_new_outputs)
     self._policy_rollout_out = {}
     self._policy_eval_out = None       # evaluate_policy(): the three [B] columns
+    self._linear_eval_out = None       # evaluate_linear(): the three [B] columns and the final observation rows
     self._state_alt = None             # pipelined rollouts: the scratch state column (allocated on first use)
     self._row_buf = None               # the row scratch of _row_scratch() (allocated on first use)
     self._dev_index = self._device.index
@@ -922,6 +925,89 @@ class Environment(dm_env.EnvironmentBase):
     args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), out,
             self._info.data_ptr())
     self._launch_steps(getattr(_native.lib, self._policy_eval_abi), args, int(num_steps), 'evaluate_policy')
+    return ev
+
+  _linear_eval_abi = None   # subclass: the C-ABI entry point of evaluate_linear (cartpole, swing-up, mountain_car)
+
+  def _check_evaluate_linear(self, weights, observation, num_steps, policy_index, epsilon, explore_seed):
+    """The refusals of evaluate_linear(): all of them before any GPU use, nothing allocated."""
+    what, name = 'evaluate_linear', type(self).__name__
+    if self._linear_eval_abi is None:
+      raise ValueError(f'{name} has no {what}() (cartpole, cartpole_swingup and mountain_car only)')
+    if self._scalar:
+      raise ValueError(f'{what}() needs the batched view (batch=B)')
+    if self._rng_mode != 'philox':
+      raise ValueError(f"{what}() needs the counter-based draw stream (rng='philox')")
+    if self._logging is not None:
+      raise ValueError(f'{what}() is not available with Logging enabled')
+    if self._wrap[0] != _native.WRAP_NONE:
+      raise ValueError(f'{what}() is not available under a reward wrapper')
+    if self._grouped_by is not None:
+      raise RuntimeError(f'{what}() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
+    if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
+      raise ValueError(f'{what}: num_steps must be an integer >= 1, got {num_steps!r}')
+    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
+      raise ValueError(f'{what}: epsilon must be a number in [0, 1], got {epsilon!r}')
+    if isinstance(explore_seed, bool) or not isinstance(explore_seed, (int, np.integer)) or not 0 <= int(explore_seed) < (1 << 64):
+      raise ValueError(f'{what}: explore_seed must be an integer in [0, 2^64), got {explore_seed!r}')
+    A, D = self._num_actions, int(np.prod(self._obs_shape))
+    if (not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.device != self._device or weights.dim() not in (2, 3)
+        or tuple(weights.shape[-2:]) != (A, D + 1) or weights.numel() == 0 or not weights.is_contiguous()):
+      raise ValueError(f'{what}: weights must be a contiguous float32 tensor of shape ({A}, {D + 1}) or (P, {A}, {D + 1}) on '
+                       f'{self._device} (column {D} is the bias)')
+    if (not torch.is_tensor(observation) or observation.dtype != torch.float32 or observation.device != self._device
+        or tuple(observation.shape) not in ((self._batch,) + self._obs_shape, (self._batch, D)) or not observation.is_contiguous()):
+      raise ValueError(f'{what}: observation must be a contiguous float32 tensor of shape {(self._batch,) + self._obs_shape} or '
+                       f'({self._batch}, {D}) on {self._device}: the observation of the last TimeStep')
+    P = 1 if weights.dim() == 2 else int(weights.shape[0])
+    if P == 1:
+      if policy_index is not None:
+        raise ValueError(f'{what}: policy_index names the row of a population of weight matrices; with one matrix it must be None')
+    elif (not torch.is_tensor(policy_index) or policy_index.dtype != torch.int32 or policy_index.device != self._device
+          or tuple(policy_index.shape) != (self._batch,) or not policy_index.is_contiguous()):
+      raise ValueError(f'{what}: a population of {P} weight matrices needs policy_index, a contiguous int32 tensor of shape '
+                       f'({self._batch},) on {self._device}')
+    return P
+
+  def evaluate_linear(self, weights, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """The closed loop of a linear agent in ONE launch, returns only (Cartpole, CartpoleSwingup and MountainCar, batched
+    view, counter-based draws, no wrapper).  The call equals, bit for bit in everything it leaves behind and returns,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else select(weights[row], obs)
+                           ts = step(a); obs = ts.observation
+
+    weights: float32 device tensor [A, D+1] (one matrix for all lanes) or [P, A, D+1] (a population; `policy_index`, int32
+    [B], names each lane's matrix and is clamped to [0, P-1]); A = 3 actions, D the observation length (mountain_car 3,
+    cartpole 6, swing-up 8), column D the bias.  select is utils.observations.linear_select: l_a = w[a][D], then
+    l_a = l_a + w[a][d] * obs[d] for d = 0..D-1 in float32 with every multiply and add rounded on its own; the largest
+    logit wins, the lowest index wins a tie, a NaN never wins.  With epsilon > 0 a lane that does not reset draws U() and,
+    if U < epsilon, takes RandInt(3) instead: stream 2 of (explore_seed, global lane id, call index), as in rollout_policy.
+    observation: float32 device tensor [B, *obs_shape] or [B, D], the observation of the last TimeStep — from reset(),
+    step(), rollout(...).observation[-1] or a previous result's `.observation` (it is an argument because cartpole's observed
+    sine / cosine are carried from step to step, not recomputed from the stored angle).  A lane that resets on the first
+    step — fresh, after LAST, marked by mark_reset() — never reads its row.  Returns `LinearEvaluation(episodes int32 [B],
+    return_sum f64 [B], episode_return_sum f64 [B], observation f32 [B, *obs_shape])`: the three columns as
+    evaluate_policy() defines them, from the float64 reward of each step, and the observation of step T-1, written once
+    after the loop.  The buffers are cached per environment and overwritten by the next call; passing `.observation` back
+    in is legal.  State, bsuite_info(), episode_counters() and the call index are left as T step() calls with the same
+    actions leave them; calls interleave freely with step / rollout / mark_reset / reset."""
+    P = self._check_evaluate_linear(weights, observation, num_steps, policy_index, epsilon, explore_seed)
+    self._ensure_allocated()
+    if self._linear_eval_out is None:
+      self._linear_eval_out = LinearEvaluation(
+          episodes=torch.empty(self._batch, dtype=torch.int32, device=self._device),
+          return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
+          episode_return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
+          observation=torch.empty((self._batch,) + self._obs_shape, dtype=torch.float32, device=self._device))
+    ev = self._linear_eval_out
+    lin = _native.Linear(weights.data_ptr(), P, policy_index.data_ptr() if policy_index is not None else None, float(epsilon),
+                         int(explore_seed), observation.data_ptr())
+    out = _native.LinearEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr(),
+                                 ev.observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(lin)) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._linear_eval_abi), args, int(num_steps), 'evaluate_linear')
     return ev
 
   def _step(self, action):

@@ -70,6 +70,7 @@ class _CartpoleBase(base.Environment):
                 steps=torch.full((self._batch,), 1 << 30, dtype=torch.int32, device=self._device))
 
   _abi_name = 'cartpole'
+  _linear_eval_abi = 'bsx_cartpole_linear_evaluate'
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

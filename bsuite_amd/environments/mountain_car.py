@@ -28,6 +28,7 @@ class MountainCar(base.Environment):
                 steps=torch.full((self._batch,), 1 << 30, dtype=torch.int32, device=self._device))
 
   _abi_name = 'mountain_car'
+  _linear_eval_abi = 'bsx_mountain_car_linear_evaluate'
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

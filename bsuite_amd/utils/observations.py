@@ -1,4 +1,5 @@
-"""Helpers for index observations (observation_mode='index' of deep_sea and catch).
+"""Helpers for index observations (observation_mode='index' of deep_sea and catch) and for linear policies on the float
+observations of the physics families (`env.evaluate_linear`).
 
 An index observation names the hot cells of a one-hot board: int32 `[..., K]`, each entry a flat cell number of the
 dense board (`env.board_shape`) or -1 for "no cell" (deep_sea's all-zero terminal board).  Pure torch: they work on
@@ -58,3 +59,28 @@ def index_embedding(index: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
   rows of ball and paddle are summed, also when they name the same cell — there the dense board holds ONE 1, so the
   two forms differ on the step where the paddle catches the ball; use index_to_dense where that matters."""
   return table[index.to(torch.int64) + 1].sum(dim=-2)
+
+
+def linear_select(weights: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
+  """The greedy action `[B]` (int32) of a linear policy on float observations, exactly as `env.evaluate_linear` selects it
+  inside its kernel (csrc/bsx_linear.h).  `weights` is float32 `[A, D+1]` (one matrix) or `[B, A, D+1]` (lane b's own
+  matrix, e.g. `population[policy_index.clamp(0, P - 1).long()]`), column D the bias; `obs` is float32 `[B, *obs_shape]`
+  with D elements per lane.
+
+    l_a = w[a][D]; for d = 0..D-1: l_a = l_a + w[a][d] * obs[d]        float32, every multiply and every add rounded on its
+                                                                       own: separate torch ops, never addcmul or matmul
+    best = 0; for a = 1..A-1: if l_a > l_best: best = a                the lowest index wins a tie, a NaN never wins"""
+  o = obs.reshape(obs.shape[0], -1)
+  D = int(o.shape[1])
+  w = weights if weights.dim() == 3 else weights.unsqueeze(0).expand(o.shape[0], -1, -1)
+  logits = w[:, :, D].clone()
+  for d in range(D):
+    prod = w[:, :, d] * o[:, d:d + 1]
+    logits = logits + prod
+  best = torch.zeros(o.shape[0], dtype=torch.int32, device=o.device)
+  l_best = logits[:, 0]
+  for a in range(1, int(w.shape[1])):
+    better = logits[:, a] > l_best
+    best = torch.where(better, torch.full_like(best, a), best)
+    l_best = torch.where(better, logits[:, a], l_best)
+  return best

@@ -78,6 +78,12 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'evaluate_policy() is not available through {type(self).__name__}: the fused policy evaluation has no '
                      'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
 
+  def evaluate_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused, like evaluate_policy: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError(f'evaluate_linear() is not available through {type(self).__name__}: the fused linear evaluation has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -498,6 +504,12 @@ class ImageObservation(dm_env.EnvironmentBase):
     del policy, num_steps, kwargs
     raise ValueError('evaluate_policy() is not available through ImageObservation: the fused policy evaluation looks its '
                      'actions up by index observations; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused: the fused linear evaluation reads the raw environment's float rows, never images (base.Environment.evaluate_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError('evaluate_linear() is not available through ImageObservation: the fused linear evaluation selects its '
+                     'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

@@ -432,6 +432,48 @@ int bsx_mountain_car_step(const bsx_mountain_car_t* cfg, const bsx_call_t* call,
                           const int32_t* action, float* state, int32_t* steps,
                           bsx_timestep_t out, double* info);
 
+/* ---- linear evaluation: a fused closed loop from a linear policy, returns only (cartpole, swing-up, mountain_car; v12,
+ *      additive) --------------------------------------------------------------------------------
+ * n_steps consecutive step() calls in ONE launch whose actions are the argmax of a linear map of the lane's own float
+ * observation.  D is the family's row length (mountain_car 3, cartpole 6, swing-up 8), A = 3 its actions.  Per step
+ * t = 0 .. n_steps-1 and lane i, with o = the lane's row of observation_in at t = 0 and the row of step t-1 after it:
+ *     a = 0                                   if the lane resets on this call (fresh, after LAST, or marked by
+ *                                             bsx_lane_reset_mark: the reset_next bit of its steps word)
+ *       = RandInt(3)                          else if epsilon > 0 and U() < epsilon
+ *       = argmax_a l_a                        else, with l_a = w[a][D]; for d = 0 .. D-1: l_a = l_a + w[a][d] * o[d]
+ *                                             in float32, every multiply and every add rounded on its own (no FMA); the
+ *                                             lowest index wins a tie and a NaN never wins (csrc/bsx_linear.h)
+ *     then exactly step(a).
+ * w = weights + row(i) * A * (D + 1); row(i) = 0 when n_policies == 1, else policy_index[i] clamped to
+ * [0, n_policies - 1].  U() and RandInt come from stream BSX_STREAM_POLICY of (explore_seed, global lane id, the step's
+ * call index), as for bsx_<family>_policy_rollout; nothing is drawn with epsilon == 0 or on a step that resets.  A lane
+ * that resets on the first step does not read its row of observation_in.  No TimeStep is written: the outputs are the
+ * three columns of bsx_policy_eval_t — same definitions, same step order, from the f64 reward of the step — and
+ * observation_out [n_lanes, D], the row of step n_steps - 1, written once after the last step (a thread reads its row
+ * of observation_in before it writes its row of observation_out: the two may be the same buffer).  state, steps, info,
+ * counters and the call index end up bit for bit as n_steps bsx_<family>_step calls with the same actions leave them.
+ * BSX_EMODE (all refusals come before any device work): an observation code or BSX_CALL_OBS_INDEX in the flags, logging,
+ * a reward wrapper, MT19937 columns, reward_f64, obs_paint, state_alt, an action ring or force_reset is set.
+ * BSX_EINVAL: n_steps < 1, n_lanes < 0, n_policies < 1.  BSX_ERANGE: epsilon outside [0, 1] (or NaN), cfg outside the
+ * family's range.  BSX_ENULL: a null pointer, policy_index included when n_policies > 1.  n_lanes == 0 returns 0 and
+ * launches nothing.  Asynchronous on call->hip_stream, no allocation, no synchronisation, graph-capturable. */
+typedef struct {
+  const float* weights;         /* device [n_policies, 3, D + 1], column D is the bias            */
+  int32_t n_policies;
+  const int32_t* policy_index;  /* device [n_lanes] or NULL when n_policies == 1                  */
+  double epsilon;
+  uint64_t explore_seed;
+  const float* observation_in;  /* device [n_lanes, D]: the observation of the last TimeStep      */
+} bsx_linear_t;
+typedef struct {
+  int32_t* episodes; double* return_sum; double* episode_return_sum;   /* device [n_lanes] each, as bsx_policy_eval_t */
+  float* observation_out;                                              /* device [n_lanes, D]                         */
+} bsx_linear_eval_t;
+int bsx_cartpole_linear_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                 float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
+int bsx_mountain_car_linear_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                     float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */
