@@ -122,8 +122,16 @@ class Linear(ctypes.Structure):
               ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64), ('observation_in', ctypes.c_void_p)]
 
 
+class Mlp(ctypes.Structure):
+  """bsx_mlp_t: the hidden-layer policy of bsx_<family>_mlp_evaluate."""
+  _fields_ = [('w1', ctypes.c_void_p), ('w2', ctypes.c_void_p), ('hidden', ctypes.c_int32), ('n_policies', ctypes.c_int32),
+              ('policy_index', ctypes.c_void_p), ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64),
+              ('observation_in', ctypes.c_void_p)]
+
+
 class LinearEvalPtrs(ctypes.Structure):
-  """bsx_linear_eval_t: the three output columns and the final observation rows of bsx_<family>_linear_evaluate."""
+  """bsx_linear_eval_t: the three output columns and the final observation rows of bsx_<family>_linear_evaluate and
+  bsx_<family>_mlp_evaluate."""
   _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p),
               ('observation_out', ctypes.c_void_p)]
 
@@ -167,6 +175,7 @@ class MountainCarCfg(ctypes.Structure):
   _fields_ = [('max_steps', ctypes.c_int32), ('_pad', ctypes.c_int32)]
 
 
+MLP_MAX_HIDDEN = 64   # BSX_MLP_MAX_HIDDEN (csrc/bsx_mlp.h)
 IMAGE_SMALL, IMAGE_BILINEAR = 0, 1
 IMAGE_MAX_RADIUS = 64
 
@@ -223,12 +232,16 @@ _SIGS = {
                            TimeStepPtrs, _P], ctypes.c_int),
     'bsx_cartpole_linear_evaluate': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), ctypes.POINTER(Linear), _P, _P,
                                       LinearEvalPtrs, _P], ctypes.c_int),
+    'bsx_cartpole_mlp_evaluate': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp), _P, _P,
+                                   LinearEvalPtrs, _P], ctypes.c_int),
     'bsx_mnist_step': ([ctypes.POINTER(MnistCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                        ctypes.c_int),
     'bsx_mountain_car_step': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), _P, _P, _P,
                                TimeStepPtrs, _P], ctypes.c_int),
     'bsx_mountain_car_linear_evaluate': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), ctypes.POINTER(Linear), _P, _P,
                                           LinearEvalPtrs, _P], ctypes.c_int),
+    'bsx_mountain_car_mlp_evaluate': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp), _P, _P,
+                                       LinearEvalPtrs, _P], ctypes.c_int),
 }
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({

@@ -716,12 +716,11 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_advance_delta_kernel(const type
   bsx_flush_counts(a.ctl, s_cnt, blockIdx.x);
 }
 
-// Degenerate boards (cells < 4: a 16-byte chunk spans several lanes): one float per thread.
+// Degenerate boards (cells < 4: a 16-byte chunk spans several lanes): one float per thread — the body of
+// bsx_hot_cells_kernel (misc.hip), which serves both families.
 template <class HotFn>
-__global__ void __launch_bounds__(BSX_BLOCK) bsx_hot_stream_tiny_kernel(float* __restrict__ obs,
-                                                                        const int32_t* __restrict__ state,
-                                                                        int64_t n_lanes, uint32_t cells,
-                                                                        HotFn fn) {
+__device__ __forceinline__ void bsx_hot_cells_body(float* __restrict__ obs, const int32_t* __restrict__ state, int64_t n_lanes,
+                                                   uint32_t cells, const HotFn& fn) {
   const uint64_t F = (uint64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
   if (F >= (uint64_t)n_lanes * cells) return;
   const uint64_t lane = F / cells;

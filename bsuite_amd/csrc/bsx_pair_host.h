@@ -37,6 +37,11 @@ static inline int bsx_launch_advance_delta(const typename Fam::args& a, const Ho
   return 0;
 }
 
+// Launches bsx_hot_cells_kernel (misc.hip): the one-float-per-thread writer of a dense observation [n_lanes x cells] of
+// `family` (BSX_FAM_DEEP_SEA: p0 = N; BSX_FAM_CATCH: p0 = rows, p1 = columns), at any 4-byte aligned address.
+int bsx_launch_hot_cells(float* obs, const int32_t* state, int64_t n_lanes, uint32_t cells, int32_t family, int32_t p0, int32_t p1,
+                         hipStream_t st);
+
 // Launches the split-phase observation writer: K stores per thread, 256 threads per workgroup — each family's measured
 // optimum (profiles/r01/sweep_stream_*.log) — in the wave-contiguous order.  (That order is a run-time argument that is
 // always 1: folded into the kernel at compile time, the compiler schedules the headline's stream differently and it ran
@@ -47,12 +52,8 @@ static inline int bsx_launch_hot_stream(float* obs, const int32_t* state, int64_
   const uint64_t total = (uint64_t)n_lanes * cells;
   // 4-byte stores for degenerate boards and for an observation slice that does not start on a 16-byte
   // boundary (rollout slice t of an odd B x cells: t*B*cells*4 bytes into the [T,B,cells] array)
-  if (cells < 4u || (reinterpret_cast<uintptr_t>(obs) & 15u) != 0) {
-    const uint64_t blocks = bsx_blocks_of(total);
-    if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
-    bsx_hot_stream_tiny_kernel<HotFn><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(obs, state, n_lanes, cells, fn);
-    return 0;
-  }
+  if (cells < 4u || (reinterpret_cast<uintptr_t>(obs) & 15u) != 0)
+    return bsx_launch_hot_cells(obs, state, n_lanes, cells, HotFn::FAMILY, fn.geom0(), fn.geom1(), st);
   const bsx_div64 dv = bsx_make_div64(cells);
   const uint64_t per_block = (uint64_t)K * 4 * BSX_BLOCK;
   const uint64_t blocks = (total + per_block - 1) / per_block;

@@ -4,6 +4,7 @@
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
 #include "bsx_linear_score.h"
+#include "bsx_mlp_returns.h"
 #include "cartpole_env.h"
 
 // The parameters derived from a cfg on the host in f64, rounded once; BSX_ERANGE for a cfg outside the family's range.
@@ -54,6 +55,19 @@ extern "C" int bsx_cartpole_linear_evaluate(const bsx_cartpole_t* cfg, const bsx
   a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
   a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
   return bsx_linear_score_call(e, BSX_FAM_CARTPOLE, call, linear, out);
+}
+
+extern "C" int bsx_cartpole_mlp_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, float* state,
+                                          int32_t* steps, bsx_linear_eval_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || mlp == nullptr) return BSX_ENULL;
+  bsx_mlp_returns_args e;
+  cartpole_env::args* a = &e.fam.cartpole;
+  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
+  if (rc == 0) rc = bsx_check_mlp_call(call, mlp, state, steps, out, info, cfg->time_frac);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
+  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+  return bsx_mlp_returns_call(e, BSX_FAM_CARTPOLE, call, mlp, out);
 }
 
 extern "C" int bsx_group_set_cartpole(bsx_group_t* g, int32_t index, const bsx_cartpole_t* cfg, const bsx_call_t* call,

@@ -47,6 +47,38 @@ int bsx_launch_index_decode(int32_t* rows, const int32_t* state, int64_t n_lanes
   return 0;
 }
 
+// The dense observation of a degenerate board (fewer than 4 cells) or at an address off the 16-byte grid
+// (bsx_launch_hot_stream): ONE kernel for deep_sea and catch, off every measured path.  The arguments are a tagged struct —
+// `family` says which decoder of `fn` is set — and the family is a uniform switch.
+struct bsx_hot_cells_args {
+  float* obs;
+  const int32_t* state;
+  int64_t n_lanes;
+  uint32_t cells;
+  int32_t family;
+  union {
+    deep_sea_hot deep_sea;
+    catch_hot catch_;
+  } fn;
+};
+
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_hot_cells_kernel(const bsx_hot_cells_args a) {
+  if (a.family == BSX_FAM_DEEP_SEA) bsx_hot_cells_body(a.obs, a.state, a.n_lanes, a.cells, a.fn.deep_sea);
+  else bsx_hot_cells_body(a.obs, a.state, a.n_lanes, a.cells, a.fn.catch_);
+}
+
+int bsx_launch_hot_cells(float* obs, const int32_t* state, int64_t n_lanes, uint32_t cells, int32_t family, int32_t p0, int32_t p1,
+                         hipStream_t st) {
+  const uint64_t blocks = (uint64_t)bsx_blocks_of((int64_t)((uint64_t)n_lanes * cells));
+  if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
+  bsx_hot_cells_args a;
+  a.obs = obs; a.state = state; a.n_lanes = n_lanes; a.cells = cells; a.family = family;
+  if (family == BSX_FAM_DEEP_SEA) a.fn.deep_sea = deep_sea_hot{p0};
+  else a.fn.catch_ = catch_hot{p0, p1};
+  bsx_hot_cells_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(a);
+  return 0;
+}
+
 // evaluate_policy (bsx_<family>_policy_evaluate): ONE kernel for deep_sea and catch — the family is a uniform switch, as in
 // the two kernels around it, and each branch is bsx_tab_eval_body (bsx_pair_device.h) instantiated for its family.  The LDS
 // holds the shared table and both families' own staging (deep_sea's action mapping; catch has none).

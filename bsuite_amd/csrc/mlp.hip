@@ -1,0 +1,28 @@
+// mlp.hip — evaluate_mlp (bsx_cartpole_mlp_evaluate, bsx_mountain_car_mlp_evaluate): ONE kernel for cartpole, swing-up and
+// mountain_car.  The family, its variant and whether the pair of matrices is shared are uniform switches, taken once per
+// launch; each branch is bsx_mlp_returns_body (bsx_mlp_returns.h) instantiated for its case.  The entry points are in
+// cartpole.hip and mountain_car.hip.
+#include "bsx_mlp_returns.h"
+
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_mlp_returns_kernel(const bsx_mlp_returns_args a) {
+  __shared__ float s_w[BSX_MLP_LDS_FLOATS];
+  __shared__ unsigned int s_cnt[2];
+  const bsx_mlp_kernarg ka = (bsx_mlp_kernarg)__builtin_amdgcn_kernarg_segment_ptr();           // = &a, in constant memory
+  const bool shared = a.p.n_policies == 1;                                // uniform
+  if (a.family == BSX_FAM_MOUNTAIN_CAR) {
+    if (shared) bsx_mlp_returns_body<bsx_mlp_mountain_car, 0, true>(ka, s_w, s_cnt);
+    else bsx_mlp_returns_body<bsx_mlp_mountain_car, 0, false>(ka, s_w, s_cnt);
+  } else if (a.fam.cartpole.cfg.swingup) {
+    if (shared) bsx_mlp_returns_body<bsx_mlp_cartpole, 1, true>(ka, s_w, s_cnt);
+    else bsx_mlp_returns_body<bsx_mlp_cartpole, 1, false>(ka, s_w, s_cnt);
+  } else {
+    if (shared) bsx_mlp_returns_body<bsx_mlp_cartpole, 0, true>(ka, s_w, s_cnt);
+    else bsx_mlp_returns_body<bsx_mlp_cartpole, 0, false>(ka, s_w, s_cnt);
+  }
+}
+
+int bsx_launch_mlp_returns(const bsx_mlp_returns_args& a, hipStream_t st) {
+  const int64_t n_lanes = a.family == BSX_FAM_MOUNTAIN_CAR ? a.fam.mountain_car.ctl.n_lanes : a.fam.cartpole.ctl.n_lanes;
+  bsx_mlp_returns_kernel<<<dim3((unsigned)bsx_blocks_of(n_lanes)), dim3(BSX_BLOCK), 0, st>>>(a);
+  return bsx_launch_status();
+}

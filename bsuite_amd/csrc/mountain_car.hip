@@ -4,6 +4,7 @@
 // file they were a 56 s single-threaded compile, the long pole of every build).
 #include "small_obs.h"
 #include "bsx_linear_score.h"
+#include "bsx_mlp_returns.h"
 #include "mountain_car_env.h"
 
 static int mountain_car_make(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, mountain_car_env::args* a) {
@@ -36,6 +37,19 @@ extern "C" int bsx_mountain_car_linear_evaluate(const bsx_mountain_car_t* cfg, c
   a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
   a->info = info; a->obs_numel = 3; a->max_steps = cfg->max_steps;
   return bsx_linear_score_call(e, BSX_FAM_MOUNTAIN_CAR, call, linear, out);
+}
+
+extern "C" int bsx_mountain_car_mlp_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                              float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || mlp == nullptr) return BSX_ENULL;
+  int rc = (cfg->max_steps < 1 || cfg->max_steps >= (1 << 30)) ? BSX_ERANGE : 0;
+  if (rc == 0) rc = bsx_check_mlp_call(call, mlp, state, steps, out, info, cfg);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_mlp_returns_args e;
+  mountain_car_env::args* a = &e.fam.mountain_car;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
+  a->info = info; a->obs_numel = 3; a->max_steps = cfg->max_steps;
+  return bsx_mlp_returns_call(e, BSX_FAM_MOUNTAIN_CAR, call, mlp, out);
 }
 
 extern "C" int bsx_group_set_mountain_car(bsx_group_t* g, int32_t index, const bsx_mountain_car_t* cfg, const bsx_call_t* call,

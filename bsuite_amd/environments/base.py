@@ -178,7 +178,7 @@ class Environment(dm_env.EnvironmentBase):
     self._rollout_out = {}             # rollout() / rollout_policy(): output buffers per T (_new_outputs)
     self._policy_rollout_out = {}
     self._policy_eval_out = None       # evaluate_policy(): the three [B] columns
-    self._linear_eval_out = None       # evaluate_linear(): the three [B] columns and the final observation rows
+    self._linear_eval_out = None       # evaluate_linear() / evaluate_mlp(): the three [B] columns and the final observation rows
     self._state_alt = None             # pipelined rollouts: the scratch state column (allocated on first use)
     self._row_buf = None               # the row scratch of _row_scratch() (allocated on first use)
     self._dev_index = self._device.index
@@ -929,10 +929,11 @@ class Environment(dm_env.EnvironmentBase):
 
   _linear_eval_abi = None   # subclass: the C-ABI entry point of evaluate_linear (cartpole, swing-up, mountain_car)
 
-  def _check_evaluate_linear(self, weights, observation, num_steps, policy_index, epsilon, explore_seed):
-    """The refusals of evaluate_linear(): all of them before any GPU use, nothing allocated."""
-    what, name = 'evaluate_linear', type(self).__name__
-    if self._linear_eval_abi is None:
+  def _check_fused_eval(self, what, abi, num_steps, epsilon, explore_seed):
+    """What evaluate_linear() and evaluate_mlp() refuse alike, before they look at a policy: the view, the family, the modes
+    and the scalars."""
+    name = type(self).__name__
+    if abi is None:
       raise ValueError(f'{name} has no {what}() (cartpole, cartpole_swingup and mountain_car only)')
     if self._scalar:
       raise ValueError(f'{what}() needs the batched view (batch=B)')
@@ -950,24 +951,50 @@ class Environment(dm_env.EnvironmentBase):
       raise ValueError(f'{what}: epsilon must be a number in [0, 1], got {epsilon!r}')
     if isinstance(explore_seed, bool) or not isinstance(explore_seed, (int, np.integer)) or not 0 <= int(explore_seed) < (1 << 64):
       raise ValueError(f'{what}: explore_seed must be an integer in [0, 2^64), got {explore_seed!r}')
-    A, D = self._num_actions, int(np.prod(self._obs_shape))
-    if (not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.device != self._device or weights.dim() not in (2, 3)
-        or tuple(weights.shape[-2:]) != (A, D + 1) or weights.numel() == 0 or not weights.is_contiguous()):
-      raise ValueError(f'{what}: weights must be a contiguous float32 tensor of shape ({A}, {D + 1}) or (P, {A}, {D + 1}) on '
-                       f'{self._device} (column {D} is the bias)')
+
+  def _is_eval_weight(self, w, dims, tail):
+    """A contiguous, non-empty float32 tensor on the environment's device with `dims` dimensions, the last two `tail`."""
+    return (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == self._device and w.dim() in dims
+            and tuple(w.shape[-2:]) == tail and w.numel() != 0 and w.is_contiguous())
+
+  def _check_fused_eval_rows(self, what, observation, P, policy_index, noun, one):
+    """... and after it: the observation rows and, for a population of P, its policy_index."""
+    D = int(np.prod(self._obs_shape))
     if (not torch.is_tensor(observation) or observation.dtype != torch.float32 or observation.device != self._device
         or tuple(observation.shape) not in ((self._batch,) + self._obs_shape, (self._batch, D)) or not observation.is_contiguous()):
       raise ValueError(f'{what}: observation must be a contiguous float32 tensor of shape {(self._batch,) + self._obs_shape} or '
                        f'({self._batch}, {D}) on {self._device}: the observation of the last TimeStep')
-    P = 1 if weights.dim() == 2 else int(weights.shape[0])
     if P == 1:
       if policy_index is not None:
-        raise ValueError(f'{what}: policy_index names the row of a population of weight matrices; with one matrix it must be None')
+        raise ValueError(f'{what}: policy_index names the row of a population of {noun}; with one {one} it must be None')
     elif (not torch.is_tensor(policy_index) or policy_index.dtype != torch.int32 or policy_index.device != self._device
           or tuple(policy_index.shape) != (self._batch,) or not policy_index.is_contiguous()):
-      raise ValueError(f'{what}: a population of {P} weight matrices needs policy_index, a contiguous int32 tensor of shape '
+      raise ValueError(f'{what}: a population of {P} {noun} needs policy_index, a contiguous int32 tensor of shape '
                        f'({self._batch},) on {self._device}')
     return P
+
+  def _check_evaluate_linear(self, weights, observation, num_steps, policy_index, epsilon, explore_seed):
+    """The refusals of evaluate_linear(): all of them before any GPU use, nothing allocated."""
+    what = 'evaluate_linear'
+    self._check_fused_eval(what, self._linear_eval_abi, num_steps, epsilon, explore_seed)
+    A, D = self._num_actions, int(np.prod(self._obs_shape))
+    if not self._is_eval_weight(weights, (2, 3), (A, D + 1)):
+      raise ValueError(f'{what}: weights must be a contiguous float32 tensor of shape ({A}, {D + 1}) or (P, {A}, {D + 1}) on '
+                       f'{self._device} (column {D} is the bias)')
+    P = 1 if weights.dim() == 2 else int(weights.shape[0])
+    return self._check_fused_eval_rows(what, observation, P, policy_index, 'weight matrices', 'matrix')
+
+  def _fused_eval_out(self):
+    """The result buffers of evaluate_linear() and evaluate_mlp(): one set per environment, shared by the two calls."""
+    if self._linear_eval_out is None:
+      self._linear_eval_out = LinearEvaluation(
+          episodes=torch.empty(self._batch, dtype=torch.int32, device=self._device),
+          return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
+          episode_return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
+          observation=torch.empty((self._batch,) + self._obs_shape, dtype=torch.float32, device=self._device))
+    ev = self._linear_eval_out
+    return ev, _native.LinearEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr(),
+                                      ev.observation.data_ptr())
 
   def evaluate_linear(self, weights, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
     """The closed loop of a linear agent in ONE launch, returns only (Cartpole, CartpoleSwingup and MountainCar, batched
@@ -994,20 +1021,60 @@ class Environment(dm_env.EnvironmentBase):
     actions leave them; calls interleave freely with step / rollout / mark_reset / reset."""
     P = self._check_evaluate_linear(weights, observation, num_steps, policy_index, epsilon, explore_seed)
     self._ensure_allocated()
-    if self._linear_eval_out is None:
-      self._linear_eval_out = LinearEvaluation(
-          episodes=torch.empty(self._batch, dtype=torch.int32, device=self._device),
-          return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
-          episode_return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
-          observation=torch.empty((self._batch,) + self._obs_shape, dtype=torch.float32, device=self._device))
-    ev = self._linear_eval_out
+    ev, out = self._fused_eval_out()
     lin = _native.Linear(weights.data_ptr(), P, policy_index.data_ptr() if policy_index is not None else None, float(epsilon),
                          int(explore_seed), observation.data_ptr())
-    out = _native.LinearEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr(),
-                                 ev.observation.data_ptr())
     args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(lin)) + \
         tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
     self._launch_steps(getattr(_native.lib, self._linear_eval_abi), args, int(num_steps), 'evaluate_linear')
+    return ev
+
+  _mlp_eval_abi = None   # subclass: the C-ABI entry point of evaluate_mlp (cartpole, swing-up, mountain_car)
+
+  def _check_evaluate_mlp(self, w1, w2, observation, num_steps, policy_index, epsilon, explore_seed):
+    """The refusals of evaluate_mlp(): all of them before any GPU use, nothing allocated.  Returns (P, H)."""
+    what = 'evaluate_mlp'
+    self._check_fused_eval(what, self._mlp_eval_abi, num_steps, epsilon, explore_seed)
+    A, D, Hmax = self._num_actions, int(np.prod(self._obs_shape)), _native.MLP_MAX_HIDDEN
+    H = int(w1.shape[-2]) if torch.is_tensor(w1) and w1.dim() in (2, 3) else 0
+    if not 1 <= H <= Hmax or not self._is_eval_weight(w1, (2, 3), (H, D + 1)):
+      raise ValueError(f'{what}: w1 must be a contiguous float32 tensor of shape (H, {D + 1}) or (P, H, {D + 1}) on {self._device} '
+                       f'with 1 <= H <= {Hmax} hidden units (column {D} is the bias)')
+    if not self._is_eval_weight(w2, (w1.dim(),), (A, H + 1)) or (w1.dim() == 3 and int(w2.shape[0]) != int(w1.shape[0])):
+      lead = '' if w1.dim() == 2 else f'{int(w1.shape[0])}, '
+      raise ValueError(f'{what}: w2 must be a contiguous float32 tensor of shape ({lead}{A}, {H + 1}) on {self._device}, the '
+                       f'same population and hidden width as w1 (column {H} is the bias)')
+    P = 1 if w1.dim() == 2 else int(w1.shape[0])
+    return self._check_fused_eval_rows(what, observation, P, policy_index, 'weight pairs', 'pair'), H
+
+  def evaluate_mlp(self, w1, w2, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`evaluate_linear` for an agent with one ReLU hidden layer: the same ONE launch, the same contract, result type and
+    refusals, with another greedy action.  The call equals, bit for bit in everything it leaves behind and returns,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else mlp_select(w1[row], w2[row], obs)
+                           ts = step(a); obs = ts.observation
+
+    w1: float32 device tensor [H, D+1] (one pair for all lanes) or [P, H, D+1]; w2: [3, H+1] or [P, 3, H+1] — the same P and
+    the same H, 1 <= H <= 64, the bias in the last column of each.  With a population, `policy_index` (int32 [B], clamped to
+    [0, P-1]) names each lane's pair; with 2-D weights it must be None.  mlp_select is utils.observations.mlp_select:
+    l_a = w2[a][H]; for every hidden unit j: s = w1[j][D], then s = s + w1[j][d] * obs[d] for d = 0..D-1, h = s if s > 0 else
+    +0.0 (a NaN pre-activation gives 0), l_a = l_a + w2[a][j] * h — float32, every multiply and add rounded on its own; the
+    largest logit wins, the lowest index wins a tie, a NaN never wins.  epsilon, explore_seed, `observation` and the returned
+    `LinearEvaluation` are evaluate_linear's; the result buffers are the ones evaluate_linear uses, so `.observation` of either
+    call may be passed into either.  A shared pair is kept on chip.  A population is read from device memory by every lane on
+    every step: group the lanes by policy (policy_index non-decreasing) — the lanes of a wave then share their loads; a
+    shuffled policy_index is legal and slower.  State, bsuite_info(), episode_counters() and the call index are left as T
+    step() calls with the same actions leave them; calls interleave freely with step / rollout / evaluate_linear /
+    mark_reset / reset."""
+    P, H = self._check_evaluate_mlp(w1, w2, observation, num_steps, policy_index, epsilon, explore_seed)
+    self._ensure_allocated()
+    ev, out = self._fused_eval_out()
+    mlp = _native.Mlp(w1.data_ptr(), w2.data_ptr(), H, P, policy_index.data_ptr() if policy_index is not None else None,
+                      float(epsilon), int(explore_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp)) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp_eval_abi), args, int(num_steps), 'evaluate_mlp')
     return ev
 
   def _step(self, action):

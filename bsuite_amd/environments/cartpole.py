@@ -71,6 +71,7 @@ class _CartpoleBase(base.Environment):
 
   _abi_name = 'cartpole'
   _linear_eval_abi = 'bsx_cartpole_linear_evaluate'
+  _mlp_eval_abi = 'bsx_cartpole_mlp_evaluate'
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

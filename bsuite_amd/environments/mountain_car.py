@@ -29,6 +29,7 @@ class MountainCar(base.Environment):
 
   _abi_name = 'mountain_car'
   _linear_eval_abi = 'bsx_mountain_car_linear_evaluate'
+  _mlp_eval_abi = 'bsx_mountain_car_mlp_evaluate'
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

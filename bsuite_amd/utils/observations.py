@@ -1,5 +1,5 @@
-"""Helpers for index observations (observation_mode='index' of deep_sea and catch) and for linear policies on the float
-observations of the physics families (`env.evaluate_linear`).
+"""Helpers for index observations (observation_mode='index' of deep_sea and catch) and for linear and hidden-layer policies on
+the float observations of the physics families (`env.evaluate_linear`, `env.evaluate_mlp`).
 
 An index observation names the hot cells of a one-hot board: int32 `[..., K]`, each entry a flat cell number of the
 dense board (`env.board_shape`) or -1 for "no cell" (deep_sea's all-zero terminal board).  Pure torch: they work on
@@ -84,3 +84,39 @@ def linear_select(weights: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
     best = torch.where(better, torch.full_like(best, a), best)
     l_best = torch.where(better, logits[:, a], l_best)
   return best
+
+
+def mlp_select(w1: torch.Tensor, w2: torch.Tensor, obs: torch.Tensor, return_preactivations: bool = False):
+  """The greedy action `[B]` (int32) of a policy with one ReLU hidden layer on float observations, exactly as
+  `env.evaluate_mlp` selects it inside its kernel (csrc/bsx_mlp.h).  `w1` is float32 `[H, D+1]` and `w2` `[3, H+1]` (one
+  pair), or `[B, H, D+1]` and `[B, 3, H+1]` (lane b's own pair, e.g. `population[policy_index.clamp(0, P - 1).long()]`), the
+  bias in the last column of each; `obs` is float32 `[B, *obs_shape]` with D elements per lane.
+
+    l_a = w2[a][H]
+    for j = 0..H-1: s = w1[j][D]; for d = 0..D-1: s = s + w1[j][d] * obs[d]      float32, every multiply and every add rounded
+                    h = s if s > 0 else +0.0                                      on its own: separate torch ops, never addcmul
+                    l_a = l_a + w2[a][j] * h                                      or matmul; a NaN s gives h = 0
+    best = 0; for a = 1, 2: if l_a > l_best: best = a                             the lowest index wins a tie, a NaN never wins
+
+  With `return_preactivations` the result is `(best, s)`, `s` float32 `[B, H]`."""
+  o = obs.reshape(obs.shape[0], -1)
+  B, D = int(o.shape[0]), int(o.shape[1])
+  a1 = w1 if w1.dim() == 3 else w1.unsqueeze(0).expand(B, -1, -1)
+  a2 = w2 if w2.dim() == 3 else w2.unsqueeze(0).expand(B, -1, -1)
+  H = int(a1.shape[1])
+  s = a1[:, :, D].clone()                                    # [B, H]: all hidden units at once, each in its own d order
+  for d in range(D):
+    prod = a1[:, :, d] * o[:, d:d + 1]
+    s = s + prod
+  h = torch.where(s > 0, s, torch.zeros_like(s))
+  logits = a2[:, :, H].clone()
+  for j in range(H):
+    prod = a2[:, :, j] * h[:, j:j + 1]
+    logits = logits + prod
+  best = torch.zeros(B, dtype=torch.int32, device=o.device)
+  l_best = logits[:, 0]
+  for a in range(1, int(a2.shape[1])):
+    better = logits[:, a] > l_best
+    best = torch.where(better, torch.full_like(best, a), best)
+    l_best = torch.where(better, logits[:, a], l_best)
+  return (best, s) if return_preactivations else best

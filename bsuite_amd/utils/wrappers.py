@@ -84,6 +84,12 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'evaluate_linear() is not available through {type(self).__name__}: the fused linear evaluation has no '
                      'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
+  def evaluate_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused, like evaluate_linear: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError(f'evaluate_mlp() is not available through {type(self).__name__}: the fused hidden-layer evaluation has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -509,6 +515,12 @@ class ImageObservation(dm_env.EnvironmentBase):
     """Refused: the fused linear evaluation reads the raw environment's float rows, never images (base.Environment.evaluate_linear)."""
     del weights, observation, num_steps, kwargs
     raise ValueError('evaluate_linear() is not available through ImageObservation: the fused linear evaluation selects its '
+                     'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def evaluate_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused: the fused hidden-layer evaluation reads the raw environment's float rows, never images (base.Environment.evaluate_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError('evaluate_mlp() is not available through ImageObservation: the fused hidden-layer evaluation selects its '
                      'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
   def __getattr__(self, attr):

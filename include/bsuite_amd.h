@@ -474,6 +474,33 @@ int bsx_cartpole_linear_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* ca
 int bsx_mountain_car_linear_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
                                      float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
 
+/* ---- hidden-layer evaluation: the same fused closed loop from a policy with one ReLU hidden layer (cartpole, swing-up,
+ *      mountain_car; v12, additive) ----------------------------------------------------------------
+ * bsx_<family>_linear_evaluate with another greedy action; everything else — the reset rule, the epsilon draws, the three
+ * columns, observation_out, what is left behind, the refusals and their order — is as stated above.  With H = hidden,
+ * w1 = [H][D + 1] and w2 = [3][H + 1] (the bias in the last column of each), the greedy action of row o is
+ *     l_a = w2[a][H]                                            a = 0 .. 2
+ *     for j = 0 .. H-1:  s = w1[j][D]; for d = 0 .. D-1: s = s + w1[j][d] * o[d]
+ *                        h = (s > 0.0f) ? s : 0.0f              (ReLU: a NaN and a -0.0 pre-activation give +0.0)
+ *                        for a = 0 .. 2: l_a = l_a + w2[a][j] * h
+ *     argmax_a l_a, the lowest index wins a tie and a NaN never wins
+ * in float32, every multiply and every add rounded on its own (no FMA) (csrc/bsx_mlp.h).  Lane i takes pair row(i) of w1
+ * and of w2, row(i) as for bsx_linear_t.  A population is read from global memory by every lane on every step: lanes that
+ * are grouped by policy share their loads, lanes of one wave that name 64 different pairs do not.
+ * BSX_EINVAL also for hidden outside [1, 64] (reported where n_policies < 1 is); BSX_ENULL also for w2. */
+typedef struct {
+  const float* w1;              /* device [n_policies, hidden, D + 1], column D is the bias       */
+  const float* w2;              /* device [n_policies, 3, hidden + 1], column hidden is the bias  */
+  int32_t hidden, n_policies;
+  const int32_t* policy_index;  /* device [n_lanes], needed iff n_policies > 1                    */
+  double epsilon; uint64_t explore_seed;
+  const float* observation_in;  /* device [n_lanes, D]: the observation of the last TimeStep      */
+} bsx_mlp_t;
+int bsx_cartpole_mlp_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                              float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
+int bsx_mountain_car_mlp_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                  float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */
