@@ -243,6 +243,11 @@ _SIGS = {
     'bsx_mountain_car_mlp_evaluate': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp), _P, _P,
                                        LinearEvalPtrs, _P], ctypes.c_int),
 }
+# rollout_linear / rollout_mlp: the evaluation's arguments with a [T,B] TimeStep and the action column as the outputs
+for _fam, _cfg in (('cartpole', CartpoleCfg), ('mountain_car', MountainCarCfg)):
+  for _kind, _policy in (('linear', Linear), ('mlp', Mlp)):
+    _SIGS[f'bsx_{_fam}_{_kind}_rollout'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy), _P, _P,
+                                             TimeStepPtrs, _P, _P], ctypes.c_int)
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({
     'bsx_group_create': ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_G)], ctypes.c_int),

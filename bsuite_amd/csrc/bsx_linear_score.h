@@ -153,8 +153,10 @@ int bsx_launch_linear_score(const bsx_linear_score_args& a, hipStream_t st);
 // The refusals of bsx_<family>_linear_evaluate that do not depend on the family, in bsx_<family>_policy_evaluate's order
 // (bsx_check_policy_eval_call): modes, scalars, then — for a call with lanes — pointers.  The caller has checked cfg, call
 // and linear for null and the cfg's range; `extra` is a pointer only the family needs (cartpole's table) or any non-null.
+// `outputs_present`: every output pointer the call writes through is non-null (the evaluation's four; a recording call's
+// TimeStep and action column, bsx_trajectory.h).
 static inline int bsx_check_linear_call(const bsx_call_t* call, const bsx_linear_t* lin, const float* state, const int32_t* steps,
-                                        const bsx_linear_eval_t& out, const double* info, const void* extra) {
+                                        bool outputs_present, const double* info, const void* extra) {
   if ((call->flags & (BSX_CALL_OBS_MASK | BSX_CALL_OBS_INDEX)) != 0) return BSX_EMODE;       // float32 rows only
   if (call->logging != nullptr || call->wrap.kind != BSX_WRAP_NONE || call->stream.mt_state != nullptr ||
       call->stream.mt_pos != nullptr || call->reward_f64 != nullptr || call->obs_paint != nullptr ||
@@ -165,13 +167,20 @@ static inline int bsx_check_linear_call(const bsx_call_t* call, const bsx_linear
   if (!(lin->epsilon >= 0.0 && lin->epsilon <= 1.0)) return BSX_ERANGE;      // (NaN included)
   if (call->n_lanes == 0) return 0;
   if (lin->weights == nullptr || lin->observation_in == nullptr || state == nullptr || steps == nullptr || info == nullptr ||
-      extra == nullptr || out.episodes == nullptr || out.return_sum == nullptr || out.episode_return_sum == nullptr ||
-      out.observation_out == nullptr)
+      extra == nullptr || !outputs_present)
     return BSX_ENULL;
   if (lin->n_policies > 1 && lin->policy_index == nullptr) return BSX_ENULL;
   if (call->action_ring < 0) return BSX_EINVAL;                              // (what bsx_check_call refuses for a rollout)
   if (bsx_blocks_of(call->n_lanes) > 0x7FFFFFFF) return BSX_EINVAL;
   return 0;
+}
+
+static inline bool bsx_linear_eval_present(const bsx_linear_eval_t& out) {
+  return out.episodes != nullptr && out.return_sum != nullptr && out.episode_return_sum != nullptr && out.observation_out != nullptr;
+}
+static inline int bsx_check_linear_call(const bsx_call_t* call, const bsx_linear_t* lin, const float* state, const int32_t* steps,
+                                        const bsx_linear_eval_t& out, const double* info, const void* extra) {
+  return bsx_check_linear_call(call, lin, state, steps, bsx_linear_eval_present(out), info, extra);
 }
 
 // What the two entry points share once the family's args are in place.

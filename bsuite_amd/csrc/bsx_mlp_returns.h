@@ -170,11 +170,15 @@ int bsx_launch_mlp_returns(const bsx_mlp_returns_args& a, hipStream_t st);
 // scalars, then, for a call with lanes, pointers.  A `hidden` outside [1, BSX_MLP_MAX_HIDDEN] is reported where
 // n_policies < 1 is, and w2 is one more pointer a call with lanes needs.  (`extra` as there.)
 static inline int bsx_check_mlp_call(const bsx_call_t* call, const bsx_mlp_t* mlp, const float* state, const int32_t* steps,
-                                     const bsx_linear_eval_t& out, const double* info, const void* extra) {
+                                     bool outputs_present, const double* info, const void* extra) {
   const bool hidden_ok = mlp->hidden >= 1 && mlp->hidden <= BSX_MLP_MAX_HIDDEN;
   const bsx_linear_t lin = {mlp->w1, hidden_ok ? mlp->n_policies : 0, mlp->policy_index, mlp->epsilon, mlp->explore_seed,
                             mlp->observation_in};
-  return bsx_check_linear_call(call, &lin, state, steps, out, info, mlp->w2 != nullptr ? extra : nullptr);
+  return bsx_check_linear_call(call, &lin, state, steps, outputs_present, info, mlp->w2 != nullptr ? extra : nullptr);
+}
+static inline int bsx_check_mlp_call(const bsx_call_t* call, const bsx_mlp_t* mlp, const float* state, const int32_t* steps,
+                                     const bsx_linear_eval_t& out, const double* info, const void* extra) {
+  return bsx_check_mlp_call(call, mlp, state, steps, bsx_linear_eval_present(out), info, extra);
 }
 
 // What the two entry points share once the family's args are in place.

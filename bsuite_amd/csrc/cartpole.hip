@@ -5,6 +5,7 @@
 #include "small_obs.h"
 #include "bsx_linear_score.h"
 #include "bsx_mlp_returns.h"
+#include "bsx_trajectory.h"
 #include "cartpole_env.h"
 
 // The parameters derived from a cfg on the host in f64, rounded once; BSX_ERANGE for a cfg outside the family's range.
@@ -68,6 +69,31 @@ extern "C" int bsx_cartpole_mlp_evaluate(const bsx_cartpole_t* cfg, const bsx_ca
   a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
   a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
   return bsx_mlp_returns_call(e, BSX_FAM_CARTPOLE, call, mlp, out);
+}
+
+// rollout_linear / rollout_mlp: the two evaluations' closed loop, writing the [T,B] TimeSteps and the actions taken.
+template <class Policy>
+static int cartpole_trajectory(const bsx_cartpole_t* cfg, const bsx_call_t* call, const Policy* policy, float* state, int32_t* steps,
+                               const bsx_timestep_t& out, int32_t* actions_out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  bsx_trajectory_args e;
+  cartpole_env::args* a = &e.fam.cartpole;
+  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
+  if (rc == 0) rc = bsx_check_trajectory_call(call, policy, state, steps, out, actions_out, info, cfg->time_frac, cfg->swingup ? 8 : 6);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.out)
+  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+  return bsx_trajectory_call(e, BSX_FAM_CARTPOLE, call, policy, out, actions_out);
+}
+
+extern "C" int bsx_cartpole_linear_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear, float* state,
+                                            int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return cartpole_trajectory(cfg, call, linear, state, steps, out, actions_out, info);
+}
+
+extern "C" int bsx_cartpole_mlp_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, float* state,
+                                         int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return cartpole_trajectory(cfg, call, mlp, state, steps, out, actions_out, info);
 }
 
 extern "C" int bsx_group_set_cartpole(bsx_group_t* g, int32_t index, const bsx_cartpole_t* cfg, const bsx_call_t* call,

@@ -204,12 +204,9 @@ extern "C" int bsx_counter_add(uint64_t* counter, uint64_t delta, void* hip_stre
 // only when an episode ends (include/bsuite_amd.h, each family's "Accounting" note): this adds the part that is still
 // pending in the lane's state — what the Python classes' bsuite_info() does on the host side of the boundary.
 //   bsuite/environments/catch.py:116-117, cartpole.py:179-181, mountain_car.py:99-100
-__global__ void __launch_bounds__(BSX_BLOCK) bsuite_info_kernel(int32_t family, int32_t variant, int64_t n_lanes,
-                                                                const int32_t* __restrict__ state,
-                                                                const double* __restrict__ info, int32_t n_info,
-                                                                int32_t folded, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
-  if (i >= n_lanes) return;
+__device__ __forceinline__ void bsuite_info_body(int64_t i, int32_t family, int32_t variant, int64_t n_lanes,
+                                                 const int32_t* __restrict__ state, const double* __restrict__ info,
+                                                 int32_t n_info, int32_t folded, double* __restrict__ out) {
   double pend0 = 0.0, pend2 = 0.0;
   if (folded) {
     if (family == BSX_FAM_CATCH) {
@@ -225,6 +222,43 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsuite_info_kernel(int32_t family, 
     out[(int64_t)c * n_lanes + i] = info[(int64_t)c * n_lanes + i] + (c == 0 ? pend0 : c == 2 ? pend2 : 0.0);
 }
 
+// The draw stream of (seed, lane0 + i, step, stream_id) as the kernels consume it: n_words raw words per lane and, optionally,
+// the n_words / 2 normals made from the same words (bsx_stream_dump; the tests hold both against the oracle).
+__device__ __forceinline__ void stream_dump_body(int64_t i, uint64_t seed, uint64_t lane0, uint64_t step, uint32_t stream_id,
+                                                 int n_words, uint32_t* words, double* normals) {
+  bsx_draws d;
+  bsx_draws_init(&d, seed, lane0 + (uint64_t)i, step, stream_id);
+  for (int w = 0; w < n_words; ++w) words[i * n_words + w] = bsx_word(&d);
+  if (normals != nullptr) {
+    bsx_draws_init(&d, seed, lane0 + (uint64_t)i, step, stream_id);
+    for (int w = 0; w < n_words / 2; ++w) normals[i * (n_words / 2) + w] = bsx_normal(&d);
+  }
+}
+
+// bsx_bsuite_info and bsx_stream_dump: ONE kernel for the two cold one-lane-per-thread tools, off every timed path.  The
+// arguments are a tagged struct — `tool` says which member of `u` is set — and the tool is a uniform switch (the idiom of
+// bsx_hot_cells_kernel above); the bodies stay separate functions.
+enum { BSX_LANE_TOOL_INFO = 0, BSX_LANE_TOOL_DUMP = 1 };
+struct bsx_lane_tool_args {
+  int32_t tool;
+  int64_t n_lanes;
+  union {
+    struct { const int32_t* state; const double* info; double* out; int32_t family, variant, n_info, folded; } info;
+    struct { uint64_t seed, lane0, step; uint32_t* words; double* normals; uint32_t stream_id; int32_t n_words; } dump;
+  } u;
+};
+
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_lane_tool_kernel(const bsx_lane_tool_args a) {
+  const int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
+  if (i >= a.n_lanes) return;
+  if (a.tool == BSX_LANE_TOOL_INFO)
+    bsuite_info_body(i, a.u.info.family, a.u.info.variant, a.n_lanes, a.u.info.state, a.u.info.info, a.u.info.n_info, a.u.info.folded,
+                     a.u.info.out);
+  else
+    stream_dump_body(i, a.u.dump.seed, a.u.dump.lane0, a.u.dump.step, a.u.dump.stream_id, a.u.dump.n_words, a.u.dump.words,
+                     a.u.dump.normals);
+}
+
 extern "C" int bsx_bsuite_info(int32_t family, int32_t variant, int64_t n_lanes, const int32_t* state, const double* info,
                                int32_t n_info, int32_t folded, double* info_out, void* hip_stream) {
   if (family < BSX_FAM_DEEP_SEA || family > BSX_FAM_MNIST || n_lanes < 0 || n_info < 0 || n_info > 8) return BSX_EINVAL;
@@ -234,8 +268,10 @@ extern "C" int bsx_bsuite_info(int32_t family, int32_t variant, int64_t n_lanes,
   if (pending && state == nullptr) return BSX_ENULL;
   const int64_t blocks = bsx_blocks_of(n_lanes);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
-  bsuite_info_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
-      family, variant, n_lanes, state, info, n_info, pending ? 1 : 0, info_out);
+  bsx_lane_tool_args a;
+  a.tool = BSX_LANE_TOOL_INFO; a.n_lanes = n_lanes;
+  a.u.info = {state, info, info_out, family, variant, n_info, pending ? 1 : 0};
+  bsx_lane_tool_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(a);
   return bsx_launch_status();
 }
 
@@ -274,28 +310,16 @@ extern "C" int bsx_lane_reset_mark(int32_t family, int32_t variant, int64_t n_la
   return bsx_launch_status();
 }
 
-__global__ void __launch_bounds__(BSX_BLOCK) stream_dump_kernel(uint64_t seed, uint64_t lane0, int64_t n_lanes,
-                                                                uint64_t step, uint32_t stream_id, int n_words,
-                                                                uint32_t* words, double* normals) {
-  int64_t i = (int64_t)blockIdx.x * BSX_BLOCK + threadIdx.x;
-  if (i >= n_lanes) return;
-  bsx_draws d;
-  bsx_draws_init(&d, seed, lane0 + (uint64_t)i, step, stream_id);
-  for (int w = 0; w < n_words; ++w) words[i * n_words + w] = bsx_word(&d);
-  if (normals != nullptr) {
-    bsx_draws_init(&d, seed, lane0 + (uint64_t)i, step, stream_id);
-    for (int w = 0; w < n_words / 2; ++w) normals[i * (n_words / 2) + w] = bsx_normal(&d);
-  }
-}
-
 extern "C" int bsx_stream_dump(uint64_t seed, uint64_t lane0, int64_t n_lanes, uint64_t step, int32_t stream_id,
                                int32_t n_words, uint32_t* words, double* normals, void* hip_stream) {
   if (words == nullptr) return BSX_ENULL;
   if (n_lanes < 0 || n_words < 0 || n_words > 1024) return BSX_EINVAL;
   if (n_lanes == 0 || n_words == 0) return 0;
   const int64_t blocks = bsx_blocks_of(n_lanes);
-  stream_dump_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(
-      seed, lane0, n_lanes, step, (uint32_t)stream_id, n_words, words, normals);
+  bsx_lane_tool_args a;
+  a.tool = BSX_LANE_TOOL_DUMP; a.n_lanes = n_lanes;
+  a.u.dump = {seed, lane0, step, words, normals, (uint32_t)stream_id, n_words};
+  bsx_lane_tool_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)hip_stream>>>(a);
   return bsx_launch_status();
 }
 

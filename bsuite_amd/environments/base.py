@@ -176,7 +176,7 @@ class Environment(dm_env.EnvironmentBase):
     self._deferred_steps = None
     self._grouped_by = None            # the SweepBatch whose prepared groups hold this environment's column pointers
     self._rollout_out = {}             # rollout() / rollout_policy(): output buffers per T (_new_outputs)
-    self._policy_rollout_out = {}
+    self._policy_rollout_out = {}      # rollout_policy() / rollout_linear() / rollout_mlp(): the same per T, + the action tensor
     self._policy_eval_out = None       # evaluate_policy(): the three [B] columns
     self._linear_eval_out = None       # evaluate_linear() / evaluate_mlp(): the three [B] columns and the final observation rows
     self._state_alt = None             # pipelined rollouts: the scratch state column (allocated on first use)
@@ -973,10 +973,11 @@ class Environment(dm_env.EnvironmentBase):
                        f'({self._batch},) on {self._device}')
     return P
 
-  def _check_evaluate_linear(self, weights, observation, num_steps, policy_index, epsilon, explore_seed):
-    """The refusals of evaluate_linear(): all of them before any GPU use, nothing allocated."""
-    what = 'evaluate_linear'
-    self._check_fused_eval(what, self._linear_eval_abi, num_steps, epsilon, explore_seed)
+  def _check_evaluate_linear(self, weights, observation, num_steps, policy_index, epsilon, explore_seed, what='evaluate_linear',
+                             abi='_linear_eval_abi'):
+    """The refusals of evaluate_linear() and rollout_linear() (`what`; `abi` names the attribute that holds its entry point):
+    all of them before any GPU use, nothing allocated."""
+    self._check_fused_eval(what, getattr(self, abi), num_steps, epsilon, explore_seed)
     A, D = self._num_actions, int(np.prod(self._obs_shape))
     if not self._is_eval_weight(weights, (2, 3), (A, D + 1)):
       raise ValueError(f'{what}: weights must be a contiguous float32 tensor of shape ({A}, {D + 1}) or (P, {A}, {D + 1}) on '
@@ -1031,10 +1032,11 @@ class Environment(dm_env.EnvironmentBase):
 
   _mlp_eval_abi = None   # subclass: the C-ABI entry point of evaluate_mlp (cartpole, swing-up, mountain_car)
 
-  def _check_evaluate_mlp(self, w1, w2, observation, num_steps, policy_index, epsilon, explore_seed):
-    """The refusals of evaluate_mlp(): all of them before any GPU use, nothing allocated.  Returns (P, H)."""
-    what = 'evaluate_mlp'
-    self._check_fused_eval(what, self._mlp_eval_abi, num_steps, epsilon, explore_seed)
+  def _check_evaluate_mlp(self, w1, w2, observation, num_steps, policy_index, epsilon, explore_seed, what='evaluate_mlp',
+                          abi='_mlp_eval_abi'):
+    """The refusals of evaluate_mlp() and rollout_mlp() (`what`; `abi` names the attribute that holds its entry point): all of
+    them before any GPU use, nothing allocated.  Returns (P, H)."""
+    self._check_fused_eval(what, getattr(self, abi), num_steps, epsilon, explore_seed)
     A, D, Hmax = self._num_actions, int(np.prod(self._obs_shape)), _native.MLP_MAX_HIDDEN
     H = int(w1.shape[-2]) if torch.is_tensor(w1) and w1.dim() in (2, 3) else 0
     if not 1 <= H <= Hmax or not self._is_eval_weight(w1, (2, 3), (H, D + 1)):
@@ -1076,6 +1078,86 @@ class Environment(dm_env.EnvironmentBase):
         tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
     self._launch_steps(getattr(_native.lib, self._mlp_eval_abi), args, int(num_steps), 'evaluate_mlp')
     return ev
+
+  _linear_rollout_abi = None   # subclass: the C-ABI entry points of rollout_linear / rollout_mlp (cartpole, swing-up,
+  _mlp_rollout_abi = None      # mountain_car)
+
+  def _check_trajectory_slab(self, what):
+    """What only the recording calls refuse: a [B, D] slab the kernel's 32-bit lane offsets cannot span."""
+    D = int(np.prod(self._obs_shape))
+    if self._batch * D * 4 >= 1 << 32:
+      raise ValueError(f'{what}: a step of {self._batch} lanes x {D} floats is 4 GiB or more; split the lanes over several '
+                       'environments (lane_offset)')
+
+  def _trajectory_out(self, T):
+    """The output buffers of rollout_linear() and rollout_mlp(): one set per T, shared by the two calls, kept where
+    rollout_policy() keeps its own (no family has both): _new_outputs((T, B), ...) + the action tensor."""
+    if T not in self._policy_rollout_out:
+      actions = torch.empty((T, self._batch), dtype=torch.int32, device=self._device)
+      self._policy_rollout_out[T] = self._new_outputs((T, self._batch), dict(device=self._device)) + (actions,)
+    return self._policy_rollout_out[T]
+
+  def rollout_linear(self, weights, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`evaluate_linear` with the same arguments, recorded: the closed loop of a linear agent in ONE launch that writes the
+    trajectory (Cartpole, CartpoleSwingup and MountainCar, batched view, counter-based draws, no wrapper).  Returns
+    `(ts, actions)`: `ts` as rollout() returns it — step_type int8 [T,B], reward / discount float32 [T,B], observation
+    float32 [T,B,*obs_shape] — and `actions` int32 [T,B], the action taken at every step, epsilon draws included, 0 where
+    the lane resets.  The call equals, bit for bit in everything it returns and everything it leaves behind,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else linear_select(weights[row], obs)
+                           ts[t] = step(a); actions[t] = a; obs = ts[t].observation
+
+    so `rollout(actions)` on a twin reproduces `ts`, and a twin's evaluate_linear() with the same arguments ends in the same
+    state with `.observation == ts.observation[-1]` and `.episodes == (ts.step_type == LAST).sum(0)`.  weights, observation,
+    policy_index, epsilon and explore_seed are evaluate_linear's: the same shapes and population form, the same stream 2 of
+    (explore_seed, global lane id, call index), nothing drawn with epsilon == 0 or on a step that resets, and a lane that
+    resets on the first step never reads its row of `observation`.  Logits and log-probabilities are not outputs: a learner
+    recomputes them from `ts.observation` and `actions` (utils.observations.linear_select has the rule).  State,
+    bsuite_info(), episode_counters() and the call index are left as T step() calls leave them; calls interleave freely with
+    step / rollout / evaluate_linear / evaluate_mlp / rollout_mlp / mark_reset / reset.  Output buffers are cached per T,
+    shared with rollout_mlp(), and overwritten by the next call of the same T."""
+    what = 'rollout_linear'
+    P = self._check_evaluate_linear(weights, observation, num_steps, policy_index, epsilon, explore_seed, what=what,
+                                    abi='_linear_rollout_abi')
+    self._check_trajectory_slab(what)
+    self._ensure_allocated()
+    T = int(num_steps)
+    _, ptrs, timestep, actions = self._trajectory_out(T)
+    lin = _native.Linear(weights.data_ptr(), P, policy_index.data_ptr() if policy_index is not None else None, float(epsilon),
+                         int(explore_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(lin)) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._linear_rollout_abi), args, T, what)
+    return timestep, actions
+
+  def rollout_mlp(self, w1, w2, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`rollout_linear` for an agent with one ReLU hidden layer — `evaluate_mlp` with the same arguments, recorded: the same
+    ONE launch, the same `(ts, actions)`, contract and refusals, with another greedy action.  The call equals, bit for bit in
+    everything it returns and everything it leaves behind,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else mlp_select(w1[row], w2[row], obs)
+                           ts[t] = step(a); actions[t] = a; obs = ts[t].observation
+
+    w1: float32 device tensor [H, D+1] or [P, H, D+1]; w2: [3, H+1] or [P, 3, H+1], 1 <= H <= 64; `policy_index`, epsilon,
+    explore_seed and `observation` as in evaluate_mlp (utils.observations.mlp_select has the rule).  A shared pair is kept on
+    chip; a population is read from device memory by every lane on every step: group the lanes by policy.  `rollout(actions)`
+    on a twin reproduces `ts`; a twin's evaluate_mlp() with the same arguments ends in the same state.  Output buffers are
+    cached per T, shared with rollout_linear(), and overwritten by the next call of the same T."""
+    what = 'rollout_mlp'
+    P, H = self._check_evaluate_mlp(w1, w2, observation, num_steps, policy_index, epsilon, explore_seed, what=what,
+                                    abi='_mlp_rollout_abi')
+    self._check_trajectory_slab(what)
+    self._ensure_allocated()
+    T = int(num_steps)
+    _, ptrs, timestep, actions = self._trajectory_out(T)
+    mlp = _native.Mlp(w1.data_ptr(), w2.data_ptr(), H, P, policy_index.data_ptr() if policy_index is not None else None,
+                      float(epsilon), int(explore_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp)) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp_rollout_abi), args, T, what)
+    return timestep, actions
 
   def _step(self, action):
     raise NotImplementedError('The batched engine fuses _step/_reset into one kernel; call step().')

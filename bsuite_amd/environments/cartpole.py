@@ -72,6 +72,8 @@ class _CartpoleBase(base.Environment):
   _abi_name = 'cartpole'
   _linear_eval_abi = 'bsx_cartpole_linear_evaluate'
   _mlp_eval_abi = 'bsx_cartpole_mlp_evaluate'
+  _linear_rollout_abi = 'bsx_cartpole_linear_rollout'
+  _mlp_rollout_abi = 'bsx_cartpole_mlp_rollout'
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

@@ -30,6 +30,8 @@ class MountainCar(base.Environment):
   _abi_name = 'mountain_car'
   _linear_eval_abi = 'bsx_mountain_car_linear_evaluate'
   _mlp_eval_abi = 'bsx_mountain_car_mlp_evaluate'
+  _linear_rollout_abi = 'bsx_mountain_car_linear_rollout'
+  _mlp_rollout_abi = 'bsx_mountain_car_mlp_rollout'
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

@@ -90,6 +90,18 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'evaluate_mlp() is not available through {type(self).__name__}: the fused hidden-layer evaluation has no '
                      'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
+  def rollout_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused, like evaluate_linear: the fused trajectory records the raw environment's rewards (base.Environment.rollout_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError(f'rollout_linear() is not available through {type(self).__name__}: the fused linear rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def rollout_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused, like evaluate_mlp: the fused trajectory records the raw environment's rewards (base.Environment.rollout_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError(f'rollout_mlp() is not available through {type(self).__name__}: the fused hidden-layer rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -522,6 +534,18 @@ class ImageObservation(dm_env.EnvironmentBase):
     del w1, w2, observation, num_steps, kwargs
     raise ValueError('evaluate_mlp() is not available through ImageObservation: the fused hidden-layer evaluation selects its '
                      'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def rollout_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused: the fused linear rollout returns the raw environment's float rows, never images (base.Environment.rollout_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError('rollout_linear() is not available through ImageObservation: the fused linear rollout selects its actions '
+                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def rollout_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused: the fused hidden-layer rollout returns the raw environment's float rows, never images (base.Environment.rollout_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError('rollout_mlp() is not available through ImageObservation: the fused hidden-layer rollout selects its actions '
+                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

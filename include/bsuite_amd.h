@@ -501,6 +501,29 @@ int bsx_cartpole_mlp_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call,
 int bsx_mountain_car_mlp_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
                                   float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
 
+/* ---- fused closed-loop trajectories: the two evaluations above, recorded (cartpole, swing-up, mountain_car; v12,
+ *      additive) --------------------------------------------------------------------------------
+ * bsx_<family>_linear_evaluate / bsx_<family>_mlp_evaluate with the same policy struct, the same actions, draws and reset
+ * rule, in ONE launch — but instead of three sums the call writes what the n_steps bsx_<family>_step calls would have
+ * returned: `out` holds [n_steps, n_lanes] reward / discount / step_type and [n_steps, n_lanes, D] observation (float32
+ * rows; slab t is step t, the reward the float32 that bsx_<family>_step writes), and actions_out [n_steps, n_lanes] the
+ * action taken at every step, epsilon draws included, 0 where the lane resets.  state, steps, info, counters and the call
+ * index end up bit for bit as those n_steps calls leave them; bsx_<family>_step with n_steps and actions_out as its
+ * actions reproduces `out`.  A lane reads its row of observation_in before the first step only; nothing written is read back.
+ * Refusals are those of the evaluation, in its order; a null out.reward / discount / step_type / observation or actions_out
+ * of a call with lanes is BSX_ENULL where a null output column is there; out.observation needs the alignment of a float
+ * only.  Then: BSX_EINVAL if n_lanes * D * 4 >= 2^32 — the kernel addresses an
+ * element as {64-bit address of the step's slab} + {the lane's 32-bit byte offset}, so a [n_lanes, D] slab of 4 GiB or
+ * more is REFUSED, never wrapped (split the lanes over several calls with bsx_call_t.lane_offset). */
+int bsx_cartpole_linear_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
+int bsx_mountain_car_linear_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                    float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
+int bsx_cartpole_mlp_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                             float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
+int bsx_mountain_car_mlp_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                 float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */

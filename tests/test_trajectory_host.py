@@ -1,0 +1,404 @@
+"""CPU: rollout_linear / rollout_mlp (fused closed-loop trajectories of cartpole, swing-up and mountain_car;
+bsx_<family>_linear_rollout, bsx_<family>_mlp_rollout) — the Python methods' signatures and refusals, the four entry points'
+declarations, bindings and error codes, the kernel's source text, and the built library: the kernel budget, what paid for
+the new kernel, its resources and the instructions inside its loops.  (The decision rules themselves are bsx_linear.h and
+bsx_mlp.h, held against numpy by tests/test_linear_eval_host.py and tests/test_mlp_eval_host.py.)"""
+import ctypes
+import inspect
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import bsuite_amd
+from bsuite_amd import _native
+from bsuite_amd.environments import base, cartpole, catch, mountain_car
+from bsuite_amd.utils import wrappers
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'bsuite_amd', 'csrc')
+HEADER = os.path.join(ROOT, 'include', 'bsuite_amd.h')
+KINDS = ('linear', 'mlp')
+ENTRY = {(fam, kind): f'bsx_{fam}_{kind}_rollout' for fam in ('cartpole', 'mountain_car') for kind in KINDS}
+
+
+# ------------------------------------------------------------------------------------------ the Python entry points
+def _envs():
+  return [cartpole.Cartpole(seed=0, batch=4), cartpole.CartpoleSwingup(seed=0, batch=4), mountain_car.MountainCar(seed=0, batch=4)]
+
+
+def _dim(env):
+  return int(np.prod(env.observation_spec().shape))
+
+
+def _refused(env, kind, exc=ValueError, match=None, **kw):
+  """env.rollout_<kind>(...) raises, its message names the caller, and nothing was allocated."""
+  raw = env.raw_env if hasattr(env, 'raw_env') else env
+  name = f'rollout_{kind}'
+  obs = kw.pop('observation') if 'observation' in kw else torch.zeros((4, 3), dtype=torch.float32)
+  if kind == 'linear':
+    pol = (kw.pop('weights') if 'weights' in kw else torch.zeros((3, 4), dtype=torch.float32),)      # (None is one of the bad values)
+  else:
+    pol = (kw.pop('w1') if 'w1' in kw else torch.zeros((5, 4), dtype=torch.float32),
+           kw.pop('w2') if 'w2' in kw else torch.zeros((3, 6), dtype=torch.float32))
+  with pytest.raises(exc, match=match or name) as info:
+    getattr(env, name)(*pol, obs, kw.pop('num_steps', 4), **kw)
+  assert name in str(info.value)
+  assert not raw._allocated and not raw._policy_rollout_out                # pylint: disable=protected-access
+
+
+def test_signatures_docstrings_and_families():
+  want = dict(linear=['self', 'weights', 'observation', 'num_steps', 'policy_index', 'epsilon', 'explore_seed'],
+              mlp=['self', 'w1', 'w2', 'observation', 'num_steps', 'policy_index', 'epsilon', 'explore_seed'])
+  for kind in KINDS:
+    fn = getattr(base.Environment, f'rollout_{kind}')
+    p = inspect.signature(fn).parameters
+    assert list(p) == want[kind]
+    assert p == inspect.signature(getattr(base.Environment, f'evaluate_{kind}')).parameters       # exactly the evaluation's arguments
+    assert [p[k].kind for k in ('policy_index', 'epsilon', 'explore_seed')] == [inspect.Parameter.KEYWORD_ONLY] * 3
+    assert p['policy_index'].default is None and p['epsilon'].default == 0.0 and p['explore_seed'].default == 0
+    for word in ('actions', 'ts[t] = step(a); actions[t] = a', f'evaluate_{kind}', f'{kind}_select', 'rollout(actions)', 'policy_index',
+                 'cached per T'):
+      assert word in fn.__doc__, (kind, word)
+    attr = f'_{kind}_rollout_abi'
+    assert getattr(cartpole.Cartpole, attr) == getattr(cartpole.CartpoleSwingup, attr) == ENTRY['cartpole', kind]
+    assert getattr(mountain_car.MountainCar, attr) == ENTRY['mountain_car', kind]
+    assert getattr(base.Environment, attr) is None and getattr(catch.Catch, attr) is None
+    # the refusals are the evaluation's, through its check functions
+    src = inspect.getsource(fn)
+    assert f'self._check_evaluate_{kind}(' in src and '_ensure_allocated()' in src
+    assert src.index(f'_check_evaluate_{kind}(') < src.index('_check_trajectory_slab(') < src.index('_ensure_allocated()')
+
+
+def test_views_families_and_modes_are_refused():
+  for kind in KINDS:
+    for env in (cartpole.Cartpole(seed=0), cartpole.CartpoleSwingup(seed=0), mountain_car.MountainCar(seed=0)):
+      _refused(env, kind, match='batched view')
+    for bsuite_id in ('bandit/0', 'deep_sea/0', 'catch/0', 'memory_len/0', 'umbrella_length/0', 'discounting_chain/0'):
+      _refused(bsuite_amd.load_from_id(bsuite_id, batch=4), kind, match='mountain_car only')
+    _refused(catch.Catch(seed=0, batch=4, observation_mode='index'), kind, match='mountain_car only')
+    for cls in (cartpole.Cartpole, cartpole.CartpoleSwingup, mountain_car.MountainCar):
+      _refused(cls(seed=0, batch=4, rng='mt19937'), kind, match='philox')
+    for env in _envs():
+      env._logging = dict(steps=None)           # what enable_logging() leaves behind (it allocates: not without a GPU)
+      _refused(env, kind, match='Logging')
+    for env in _envs():
+      env._grouped_by = object()                # what SweepBatch sets while its prepared groups hold the column pointers
+      _refused(env, kind, exc=RuntimeError, match='release_groups')
+    # a step of 4 GiB or more: the kernel's 32-bit lane offsets could not span it (the last check before anything is allocated)
+    for env in _envs():
+      env._batch = -(-(1 << 32) // (4 * _dim(env)))                        # the first batch whose [B, D] slab reaches 4 GiB
+      with pytest.raises(ValueError, match=f'rollout_{kind}: .* 4 GiB'):
+        env._check_trajectory_slab(f'rollout_{kind}')                      # pylint: disable=protected-access
+      env._batch -= 1
+      env._check_trajectory_slab(f'rollout_{kind}')                        # pylint: disable=protected-access
+      assert not env._allocated                                            # pylint: disable=protected-access
+
+
+def test_the_wrappers_refuse_instead_of_delegating():
+  for kind in KINDS:
+    name = f'rollout_{kind}'
+    for make in (lambda e: wrappers.RewardNoise(e, noise_scale=0.5, seed=1), lambda e: wrappers.RewardScale(e, reward_scale=2.0)):
+      for raw in _envs():
+        _refused(make(raw), kind, match='not available through')
+        _refused(raw, kind, match='reward wrapper')                       # ... and the raw environment knows it is wrapped
+    for bsuite_id in ('cartpole_noise/2', 'cartpole_scale/4', 'mountain_car_noise/3', 'mountain_car_scale/1'):
+      env = bsuite_amd.load_from_id(bsuite_id, batch=4)
+      assert hasattr(env, 'raw_env'), bsuite_id
+      _refused(env, kind, match='not available through')
+    # every wrapper class carries its own method (attribute delegation would reach the raw environment's)
+    for cls in (wrappers.RewardNoise, wrappers.RewardScale, wrappers.Logging, wrappers.ImageObservation):
+      fn = getattr(cls, name)
+      assert fn is not getattr(base.Environment, name) and any(name in vars(c) for c in cls.__mro__[:-1]), cls
+      args = (torch.zeros((3, 4)),) if kind == 'linear' else (torch.zeros((5, 4)), torch.zeros((3, 6)))
+      with pytest.raises(ValueError, match=name):
+        fn(object.__new__(cls), *args, torch.zeros((4, 3)), 4)
+    image = wrappers.ImageObservation(mountain_car.MountainCar(seed=0, batch=4), (84, 84, 1))
+    _refused(image, kind, match='not available through ImageObservation')
+
+
+def test_arguments_are_checked_before_any_gpu_use():
+  for env in _envs():
+    env._device = torch.device('cpu')       # the checks themselves, on host tensors: dtype, shape, contiguity
+    D, H = _dim(env), 5
+    w, pw = torch.zeros((3, D + 1)), torch.zeros((4, 3, D + 1))
+    w1, w2, p1, p2 = torch.zeros((H, D + 1)), torch.zeros((3, H + 1)), torch.zeros((4, H, D + 1)), torch.zeros((4, 3, H + 1))
+    obs = torch.zeros((4, 1, D), dtype=torch.float32)
+    idx = torch.zeros(4, dtype=torch.int32)
+    for kind, ok, pop in (('linear', dict(weights=w), dict(weights=pw)), ('mlp', dict(w1=w1, w2=w2), dict(w1=p1, w2=p2))):
+      name = f'rollout_{kind}'
+      for eps in (-0.1, 1.5, float('nan'), float('inf'), '0.1', None, True):
+        _refused(env, kind, epsilon=eps, observation=obs, match=f'{name}: epsilon', **ok)
+      for n in (0, -1, 2.0, None, '4', True):
+        _refused(env, kind, num_steps=n, observation=obs, match=f'{name}: num_steps', **ok)
+      for seed in (-1, 1 << 64, 0.5, None):
+        _refused(env, kind, explore_seed=seed, observation=obs, match=f'{name}: explore_seed', **ok)
+      for bad in (obs.to(torch.float64), obs.numpy(), torch.zeros((4, D + 1)), torch.zeros((3, 1, D)), torch.zeros(4 * D),
+                  torch.zeros((4, 2 * D))[:, ::2], None):
+        _refused(env, kind, observation=bad, match=f'{name}: observation must be', **ok)
+      _refused(env, kind, observation=torch.zeros((4, D)), policy_index=idx, match='must be None', **ok)     # ([B, D] is a legal shape)
+      for bad in (None, idx.to(torch.int64), idx.numpy(), torch.zeros(5, dtype=torch.int32), torch.zeros(8, dtype=torch.int32)[::2]):
+        _refused(env, kind, observation=obs, policy_index=bad, match='policy_index', **pop)
+    for bad in (w.to(torch.float64), w.numpy(), torch.zeros((3, D)), torch.zeros((2, D + 1)), torch.zeros((0, 3, D + 1)),
+                torch.zeros((3, 2 * (D + 1)))[:, ::2], None):
+      _refused(env, 'linear', weights=bad, observation=obs, match='rollout_linear: weights must be')
+    for bad in (w1.to(torch.float64), torch.zeros((H, D)), torch.zeros((0, D + 1)), torch.zeros((65, D + 1)), None):
+      _refused(env, 'mlp', w1=bad, w2=w2, observation=obs, match='rollout_mlp: w1 must be')
+    for bad in (w2.to(torch.float64), torch.zeros((3, H)), torch.zeros((2, H + 1)), torch.zeros((1, 3, H + 1)), None):
+      _refused(env, 'mlp', w1=w1, w2=bad, observation=obs, match='rollout_mlp: w2 must be')
+    _refused(env, 'mlp', w1=p1, w2=torch.zeros((3, 3, H + 1)), observation=obs, policy_index=idx, match='rollout_mlp: w2 must be')
+    assert not env._allocated                                                       # pylint: disable=protected-access
+  # host tensors for an environment on the GPU
+  env = mountain_car.MountainCar(seed=0, batch=4)
+  _refused(env, 'linear', weights=torch.zeros((3, 4)), observation=torch.zeros((4, 1, 3)), match='weights must be')
+  _refused(env, 'mlp', observation=torch.zeros((4, 1, 3)), match='w1 must be')
+
+
+# ------------------------------------------------------------------------------------------ the C ABI
+def test_header_binding_and_export_agree_and_the_abi_stays_v12():
+  header = open(HEADER).read()
+  assert re.search(r'#define BSX_ABI_VERSION 12\b', header)
+  assert _native.ABI_VERSION == 12 and _native.lib.bsx_abi_version() == 12
+  plain = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
+  out = subprocess.check_output(['nm', '-D', '--defined-only', _native.SO_PATH], text=True)
+  P = ctypes.c_void_p
+  text = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+  for (fam, kind), name in ENTRY.items():
+    decl = re.search(r'int ' + name + r'\(([^;]*)\);', plain)
+    assert decl, f'include/bsuite_amd.h does not declare {name}'
+    types = [re.sub(r'\s*\w+$', '', a.strip()) for a in ' '.join(decl.group(1).split()).split(',')]
+    assert types == [f'const bsx_{fam}_t*', 'const bsx_call_t*', f'const bsx_{kind}_t*', 'float*', 'int32_t*', 'bsx_timestep_t', 'int32_t*',
+                     'double*']
+    assert name in _native.EXPORTED
+    fn = getattr(_native.lib, name)
+    cfg = dict(cartpole=_native.CartpoleCfg, mountain_car=_native.MountainCarCfg)[fam]
+    policy = dict(linear=_native.Linear, mlp=_native.Mlp)[kind]
+    assert fn.argtypes == [ctypes.POINTER(cfg), ctypes.POINTER(_native.Call), ctypes.POINTER(policy), P, P, _native.TimeStepPtrs, P, P]
+    assert fn.restype is ctypes.c_int
+    assert any(l.split()[-1] == name and ' T ' in l for l in out.splitlines())
+    assert name in text, f'INTEGRATION.md does not describe {name}'
+  # no new struct: the policies and the TimeStep are the existing ones, layouts untouched
+  assert ctypes.sizeof(_native.Linear) == 48 and ctypes.sizeof(_native.Mlp) == 56 and ctypes.sizeof(_native.TimeStepPtrs) == 32
+  assert [f[0] for f in _native.TimeStepPtrs._fields_] == ['reward', 'discount', 'step_type', 'observation']     # pylint: disable=protected-access
+  # the header says which way a slab of 4 GiB goes
+  note = header[header.index('fused closed-loop trajectories'):header.index('int bsx_cartpole_linear_rollout(')]
+  assert 'n_lanes * D * 4 >= 2^32' in note and 'REFUSED' in note and 'BSX_EINVAL' in note
+
+
+def _abi_case(fam):
+  if fam == 'mountain_car':
+    return _native.MountainCarCfg(1000, 0), _native.MountainCarCfg(0, 0)
+  good = dict(swingup=0, last_step=1001, height_threshold=0.8, x_threshold=3.0, theta_dot_threshold=1.0, x_reward_threshold=1.0,
+              timescale=0.01, mass_cart=1.0, mass_pole=0.1, length=0.5, force_mag=10.0, gravity=9.8, move_cost=0.0, init_range=0.05,
+              theta_offset=0.0, time_frac=0xDEAD0008)
+  return _native.CartpoleCfg(**good), _native.CartpoleCfg(**dict(good, last_step=0))
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('fam', ['cartpole', 'mountain_car'])
+def test_argument_checks_of_the_entry_points(fam, kind):
+  """Every refusal comes before any device work: garbage stands in for device pointers, none is dereferenced.  The codes and
+  their order are those of bsx_<family>_<kind>_evaluate: null structs, the cfg, modes, scalars, pointers."""
+  fn = getattr(_native.lib, ENTRY[fam, kind])
+  cfg, bad_cfg = _abi_case(fam)
+  junk = 0xDEAD0010                                                # never mapped: a dereference would fault (16-byte aligned)
+  E = _native
+  D = 3 if fam == 'mountain_car' else 6
+
+  def call(**kw):
+    c = _native.Call(n_lanes=kw.pop('n_lanes', 4), n_steps=kw.pop('n_steps', 4), flags=kw.pop('flags', 0))
+    for k, v in kw.items():
+      setattr(c, k, v)
+    return c
+
+  def policy(**kw):
+    if kind == 'linear':
+      kw.pop('hidden', None)
+      d = dict(weights=junk, n_policies=1, policy_index=None, epsilon=0.0, explore_seed=0, observation_in=junk)
+      d.update(kw)
+      return _native.Linear(**d)
+    d = dict(w1=junk, w2=junk, hidden=5, n_policies=1, policy_index=None, epsilon=0.0, explore_seed=0, observation_in=junk)
+    d.update(kw)
+    return _native.Mlp(**d)
+
+  def run(c, q, state=junk, steps=junk, out=None, actions=junk, info=junk, cfg_=cfg):
+    out = _native.TimeStepPtrs(junk, junk, junk, junk) if out is None else out
+    return fn(ctypes.byref(cfg_) if cfg_ is not None else None, ctypes.byref(c) if c is not None else None,
+              ctypes.byref(q) if q is not None else None, state, steps, out, actions, info)
+
+  # null structs
+  assert run(call(), policy(), cfg_=None) == E.BSX_ENULL
+  assert run(None, policy()) == E.BSX_ENULL
+  assert run(call(), None) == E.BSX_ENULL
+  # BSX_EMODE: before the scalars
+  for flags in (E.CALL_OBS_INDEX, E.CALL_OBS_U8, E.CALL_OBS_F16, E.CALL_OBS_BF16, E.CALL_OBS_INDEX | E.CALL_OBS_U8):
+    assert run(call(flags=flags), policy(n_policies=-1, hidden=0)) == E.BSX_EMODE, flags
+  lg = _native.Logging()
+  assert run(call(logging=ctypes.pointer(lg)), policy(hidden=99)) == E.BSX_EMODE
+  for wrap in (E.WRAP_SCALE, E.WRAP_NOISE, E.WRAP_SCALE_NOISE, E.WRAP_NOISE_SCALE):
+    c = call()
+    c.wrap.kind = wrap
+    assert run(c, policy()) == E.BSX_EMODE, wrap
+  c = call()
+  c.stream.mt_state, c.stream.mt_pos = junk, junk
+  assert run(c, policy()) == E.BSX_EMODE
+  for member in ('reward_f64', 'obs_paint', 'state_alt'):
+    assert run(call(**{member: junk}), policy()) == E.BSX_EMODE, member
+  assert run(call(force_reset=1), policy()) == E.BSX_EMODE
+  assert run(call(action_ring=4), policy()) == E.BSX_EMODE
+  # BSX_EINVAL / BSX_ERANGE: the scalars
+  for n in (0, -1):
+    assert run(call(n_steps=n), policy()) == E.BSX_EINVAL
+  assert run(call(n_lanes=-1), policy()) == E.BSX_EINVAL
+  if kind == 'mlp':
+    for h in (0, -1, 65, 1 << 20):
+      assert run(call(), policy(hidden=h)) == E.BSX_EINVAL, h
+      assert run(call(), policy(hidden=h, epsilon=2.0)) == E.BSX_EINVAL, h            # where n_policies < 1 is: before epsilon
+      assert run(call(n_lanes=0), policy(hidden=h)) == E.BSX_EINVAL, h
+    for h in (1, 64):
+      assert run(call(n_lanes=0), policy(hidden=h)) == 0
+  for n in (0, -3):
+    assert run(call(), policy(n_policies=n)) == E.BSX_EINVAL
+  for eps in (-1e-9, 1.0000001, float('nan'), float('inf')):
+    assert run(call(), policy(epsilon=eps)) == E.BSX_ERANGE, eps
+  assert run(call(), policy(), cfg_=bad_cfg) == E.BSX_ERANGE
+  assert run(call(flags=E.CALL_OBS_INDEX), policy(), cfg_=bad_cfg) == E.BSX_ERANGE          # (the cfg comes first)
+  # n_lanes == 0: nothing to do, nothing launched, no pointer looked at
+  none = {k: None for k in (('weights',) if kind == 'linear' else ('w1', 'w2')) + ('observation_in',)}
+  assert run(call(n_lanes=0), policy(**none), state=None, steps=None, out=_native.TimeStepPtrs(0, 0, 0, 0), actions=None, info=None) == 0
+  assert run(call(n_lanes=0), policy(epsilon=2.0)) == E.BSX_ERANGE                          # ... but the scalars are
+  # BSX_ENULL: every pointer — the other ones garbage
+  for missing in none:
+    assert run(call(), policy(**{missing: None})) == E.BSX_ENULL, missing
+  for missing in ('state', 'steps', 'info'):
+    assert run(call(), policy(), **{missing: None}) == E.BSX_ENULL, missing
+  for k in range(4):                                                                        # every pointer of the TimeStep
+    ptrs = [junk] * 4
+    ptrs[k] = 0
+    assert run(call(), policy(), out=_native.TimeStepPtrs(*ptrs)) == E.BSX_ENULL, k
+  assert run(call(), policy(), actions=None) == E.BSX_ENULL                                 # ... and the action column
+  assert run(call(), policy(n_policies=2)) == E.BSX_ENULL                                   # a population without policy_index
+  if fam == 'cartpole':
+    no_table = _abi_case(fam)[0]
+    no_table.time_frac = None
+    assert run(call(), policy(), cfg_=no_table) == E.BSX_ENULL
+  assert run(call(n_lanes=1 << 40), policy()) == E.BSX_EINVAL                               # more workgroups than a grid holds
+  assert run(call(action_ring=-2), policy()) == E.BSX_EINVAL
+  # what only a call that writes [T,B] slabs refuses: a slab the 32-bit lane offsets cannot span
+  assert run(call(n_lanes=-(-(1 << 32) // (4 * D))), policy()) == E.BSX_EINVAL             # the first n_lanes whose slab reaches 4 GiB
+  assert run(call(n_lanes=1 << 31), policy()) == E.BSX_EINVAL
+
+
+# ------------------------------------------------------------------------------------------ the source text
+def test_the_kernel_body_uses_the_headers():
+  dev = open(os.path.join(CSRC, 'bsx_trajectory.h')).read()
+  body = dev[dev.index('void bsx_trajectory_body('):]
+  body = body[:body.index('\n}\n')]
+  walk = dev[dev.index('int32_t bsx_trajectory_hidden_action('):]
+  walk = walk[:walk.index('\n}\n')]
+  for call_ in ('bsx_linear_select(w, o, D)', 'bsx_trajectory_hidden_action<D>(', 'bsx_policy_draws(p.explore_seed, lane, step)',
+                'bsx_policy_clamp(k0.p.policy_index[i], k0.p.n_policies)', 'bsx_policy_select(', 'Env::reset_pending(rg)', 'bsx_pool_counts(',
+                'Env::template core<0, 0, true, false, false, V, true>(', 'Env::template load_info<V>(', 'Env::template store_info<V>(',
+                'bsx_fresh(0u)', 'bsx_trajectory_view(ka)', 'bsx_emit_values<0, 0, false, 0>(', 'bsx_trajectory_store_row<D>(',
+                'small_rollout_nt_scalars<Env>::value', 'bsx_st<BSX_OUT_SCALARS.rollout>(bsx_at_off(kt.actions_out'):
+    assert call_ in body, call_
+  for piece in ('bsx_mlp_hidden(', 'bsx_mlp_accumulate(', 'bsx_mlp_argmax('):       # the hidden-layer rule in the kernel's pieces
+    assert piece in walk, piece
+  row = dev[dev.index('void bsx_trajectory_store_row('):dev.index('// rollout_linear(T) / rollout_mlp(T).')]
+  assert 'small_obs_store_row<true>(' in row and row.count('__builtin_nontemporal_store(') == 3
+  loop = body[body.index('for (int t = 0; t < n_steps; ++t) {'):]
+  loop = loop[:loop.index('\n    }\n')]
+  assert 'core<' in loop and 'bsx_linear_select(' in loop and loop.count('bsx_trajectory_hidden_action<D>(') == 2
+  assert loop.count('bsx_st<') == 4 and 'bsx_trajectory_store_row<D>(' in loop
+  for word in ('__syncthreads', 'atomic', 's_w[', 'Env::store', 'store_info', 'observation_in', 'bsx_pool_counts'):
+    assert word not in loop, word
+  for word in ('__syncthreads', 'atomic', 'bsx_st<', 's_w['):
+    assert word not in walk, word
+  # three views: before the loop, per step, after the loop (+ the pooled counts)
+  assert body.count('bsx_trajectory_view(ka)') == 4 and loop.count('bsx_trajectory_view(ka)') == 1
+  # no second statement of either rule
+  for f in ('bsx_trajectory.h', 'trajectory.hip'):
+    text = open(os.path.join(CSRC, f)).read()
+    assert 'l_best' not in text and '> 0.0f' not in text, f
+  hip = open(os.path.join(CSRC, 'trajectory.hip')).read()
+  assert hip.count('__global__') == 1
+  assert '__global__ void __launch_bounds__(BSX_BLOCK) bsx_trajectory_kernel(const bsx_trajectory_args a)' in hip
+  for inst in ('<Fam, V, true, true>', '<Fam, V, false, true>', '<Fam, V, true, false>', '<Fam, V, false, false>'):
+    assert 'bsx_trajectory_body' + inst in hip, inst
+  for inst in ('<bsx_trajectory_mountain_car, 0>', '<bsx_trajectory_cartpole, 1>', '<bsx_trajectory_cartpole, 0>'):
+    assert 'bsx_trajectory_switch' + inst in hip, inst
+  assert open(os.path.join(CSRC, 'linear.hip')).read().count('__global__') == 1
+  assert open(os.path.join(CSRC, 'mlp.hip')).read().count('__global__') == 1
+  for (fam, _), entry in ENTRY.items():
+    assert 'extern "C" int ' + entry + '(' in open(os.path.join(CSRC, fam + '.hip')).read()
+  # what paid for the kernel: one tagged kernel for the two cold lane tools, their bodies separate functions
+  misc = open(os.path.join(CSRC, 'misc.hip')).read()
+  assert '__global__ void __launch_bounds__(BSX_BLOCK) bsx_lane_tool_kernel(const bsx_lane_tool_args a)' in misc
+  assert 'void bsuite_info_body(' in misc and 'void stream_dump_body(' in misc
+  assert 'bsuite_info_kernel' not in misc and 'stream_dump_kernel' not in misc
+  assert '__global__ void counter_add_kernel(' in misc and 'counter_add_kernel<<<dim3(1), dim3(1), 0,' in misc      # still one tiny launch
+
+
+# ------------------------------------------------------------------------------------------ the built library
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+import kernel_isa as ki  # noqa: E402  pylint: disable=wrong-import-position
+import kernel_resources as kr  # noqa: E402  pylint: disable=wrong-import-position
+
+needs_llvm = pytest.mark.skipif(not os.path.exists(os.path.join(kr.LLVM, 'clang-offload-bundler')) or shutil.which('c++filt') is None,
+                                reason='needs the ROCm LLVM tools')
+NEW = 'bsx_trajectory_kernel'
+
+
+@needs_llvm
+def test_product_library_has_the_one_new_kernel_inside_the_kernel_budget():
+  from bsuite_amd import build
+  ks = {k['name'].split('(')[0]: k for k in kr.kernels(build.build())}
+  assert len(ks) <= 186, len(ks)
+  assert [n for n in ks if 'trajectory' in n] == [NEW]                   # ONE kernel for the twelve cases
+  assert not any(w in NEW for w in ('index', 'policy', 'eval', 'linear', 'score', 'mlp', 'hot_cells', 'hot_stream_tiny', 'calib_'))
+  # what paid for it: the two cold one-lane-per-thread tools are one kernel
+  assert 'bsx_lane_tool_kernel' in ks and 'bsuite_info_kernel' not in ks and 'stream_dump_kernel' not in ks
+  assert 'counter_add_kernel' in ks
+  k = ks[NEW]
+  assert k['private_segment_fixed_size'] == 0 and k['vgpr_spill_count'] == 0 and k['sgpr_spill_count'] == 0, k
+  assert k['agpr_count'] == 0, k
+  assert k['vgpr_count'] <= 128, k
+  assert k['group_segment_fixed_size'] <= 4096, k
+
+
+@needs_llvm
+def test_stores_inside_the_loops_of_the_new_kernel_and_nothing_that_waits():
+  """Inside ANY loop of the kernel (the compiler marks a loop's blocks in its block comments): the per-step stores are there,
+  every row store and the action store is non-temporal and addressed as {scalar base} + {32-bit lane offset}; no flat, scratch
+  or buffer access, no barrier, no LDS write, no atomic, no spill reload.  The only stores that are not non-temporal are
+  mountain_car's three scalar columns (small_rollout_nt_scalars<mountain_car_env>): four branches x (2 dwords + 1 byte)."""
+  _, text = ki.kernel_text(os.path.join(CSRC, 'trajectory.hip'), NEW)
+  in_loop, inside, headers = False, [], 0
+  for l in text:
+    if re.match(r'^\.LBB\d+_\d+:', l) or l.startswith('; %bb.'):
+      in_loop = 'Loop' in l
+      headers += 'Loop Header' in l and 'Depth=1' in l
+      continue
+    s = l.strip()
+    if in_loop and s and not s.startswith(';') and not s.startswith('.'):
+      inside.append(s)
+  assert headers >= 12, headers
+  stores = [s for s in inside if s.startswith('global_store')]
+  assert len(stores) >= 12 * 5, len(stores)
+  form = r', s\[\d+:\d+\]( offset:\d+)?( nt)?$'
+  assert all(re.search(form, s) for s in stores), [s for s in stores if not re.search(form, s)]
+  wide = [s for s in stores if re.match(r'global_store_dwordx[234] ', s)]                   # the rows
+  assert len(wide) >= 12 and all(s.endswith(' nt') for s in wide), wide
+  plain = [s.split()[0] for s in stores if not s.endswith(' nt')]
+  assert sorted(plain) == ['global_store_byte'] * 4 + ['global_store_dword'] * 8, plain     # mountain_car's scalar columns
+  # 12 branches x the action column, + 8 cartpole branches x (reward, discount): dword stores, non-temporal
+  assert sum(s.startswith('global_store_dword ') and s.endswith(' nt') for s in stores) == 12 + 16
+  assert sum(s.startswith('ds_read') for s in inside) >= 6, 'the shared policy is read inside the loops'
+  bad = [s for s in inside if re.match(r'flat_|scratch_|buffer_|(global|ds)_atomic|ds_write|ds_add|ds_\w*rtn|s_barrier', s)]
+  assert not bad, bad
+  assert ki.loop_spill_reloads(text, min_depth=1) == 0
