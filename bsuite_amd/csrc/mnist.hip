@@ -20,25 +20,33 @@ __global__ void __launch_bounds__(BSX_BLOCK) mnist_advance_kernel(const mnist_ar
   mnist_advance_body(a, blockIdx.x, s_cnt);
 }
 
-__global__ void __launch_bounds__(BSX_BLOCK) mnist_advance_group_kernel(const mnist_args* __restrict__ table,
-                                                                        const bsx_group_index gi) {
-  __shared__ unsigned int s_cnt[2];
-  const bsx_group_slot w = bsx_group_find(gi, (int)blockIdx.x);
-  mnist_advance_body(table[w.seg], w.block, s_cnt);
-}
-
 template <int K>
 __global__ void __launch_bounds__(BSX_BLOCK) mnist_observe_kernel(const mnist_observe_args a) {
   __shared__ float s_lut[MNIST_LUT_FLOATS];
   mnist_observe_body<K>(a, blockIdx.x, s_lut);
 }
 
+// The two launches of a group of mnist segments alone (bsx_group_set_mnist on a BSX_FAM_MNIST group: the sweep with
+// mix_pairs off; the whole sweep and the mixed two-kernel group have kernels of their own): ONE kernel, off every timed path.
+// The arguments are a tagged struct — `phase` says which table of `table` is set — and the phase is a uniform switch (the
+// idiom of bsx_hot_cells_kernel / bsx_lane_tool_kernel, misc.hip); the bodies are the stand-alone kernels' (mnist_fam.h).
+enum { MNIST_GROUP_ADVANCE = 0, MNIST_GROUP_OBSERVE = 1 };
+struct mnist_group_args {
+  int32_t phase;
+  union {
+    const mnist_args* advance;           // device [n_segments]
+    const mnist_observe_args* observe;   // device [n_segments]
+  } table;
+  bsx_group_index gi;
+};
+
 template <int K>
-__global__ void __launch_bounds__(BSX_BLOCK) mnist_observe_group_kernel(const mnist_observe_args* __restrict__ table,
-                                                                        const bsx_group_index gi) {
+__global__ void __launch_bounds__(BSX_BLOCK) mnist_group_kernel(const mnist_group_args a) {
+  __shared__ unsigned int s_cnt[2];
   __shared__ float s_lut[MNIST_LUT_FLOATS];
-  const bsx_group_slot w = bsx_group_find(gi, (int)blockIdx.x);
-  mnist_observe_body<K>(table[w.seg], w.block, s_lut);
+  const bsx_group_slot w = bsx_group_find(a.gi, (int)blockIdx.x);
+  if (a.phase == MNIST_GROUP_ADVANCE) mnist_advance_body(a.table.advance[w.seg], w.block, s_cnt);
+  else mnist_observe_body<K>(a.table.observe[w.seg], w.block, s_lut);
 }
 
 // 4 KiB-runs per wave: 16 KiB per workgroup is a sharp optimum of the straight-line body (K = 3: 5.95, 4: 7.0, 5: 5.9, 8: 5.9 TB/s
@@ -104,12 +112,14 @@ extern "C" int bsx_mnist_step(const bsx_mnist_t* cfg, const bsx_call_t* call, co
 }
 
 static int mnist_group_launch(bsx_group* g, int phase, hipStream_t st) {
-  if (phase != 1)
-    mnist_advance_group_kernel<<<dim3((unsigned)g->total_blocks), dim3(BSX_BLOCK), 0, st>>>(
-        (const mnist_args*)g->d_args, g->index1());
+  mnist_group_args a;
+  if (phase != 1) {
+    a.phase = MNIST_GROUP_ADVANCE; a.table.advance = (const mnist_args*)g->d_args; a.gi = g->index1();
+    mnist_group_kernel<PAIR_MNIST_K><<<dim3((unsigned)g->total_blocks), dim3(BSX_BLOCK), 0, st>>>(a);
+  }
   if (phase == 0) return (int)hipGetLastError();
-  mnist_observe_group_kernel<PAIR_MNIST_K><<<dim3((unsigned)g->total_blocks2), dim3(BSX_BLOCK), 0, st>>>(
-      (const mnist_observe_args*)g->d_args2, g->index2());
+  a.phase = MNIST_GROUP_OBSERVE; a.table.observe = (const mnist_observe_args*)g->d_args2; a.gi = g->index2();
+  mnist_group_kernel<PAIR_MNIST_K><<<dim3((unsigned)g->total_blocks2), dim3(BSX_BLOCK), 0, st>>>(a);
   return (int)hipGetLastError();
 }
 

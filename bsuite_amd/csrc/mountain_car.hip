@@ -6,6 +6,7 @@
 #include "bsx_linear_score.h"
 #include "bsx_mlp_returns.h"
 #include "bsx_trajectory.h"
+#include "bsx_gumbel_device.h"
 #include "mountain_car_env.h"
 
 static int mountain_car_make(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, mountain_car_env::args* a) {
@@ -76,6 +77,33 @@ extern "C" int bsx_mountain_car_linear_rollout(const bsx_mountain_car_t* cfg, co
 extern "C" int bsx_mountain_car_mlp_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
                                              float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
   return mountain_car_trajectory(cfg, call, mlp, state, steps, out, actions_out, info);
+}
+
+// sample_linear / sample_mlp: the recording closed loop with actions drawn from softmax(logits * inv_temperature).
+template <class Policy>
+static int mountain_car_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const Policy* policy, double inv_temperature,
+                               float* state, int32_t* steps, const bsx_timestep_t& out, int32_t* actions_out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = (cfg->max_steps < 1 || cfg->max_steps >= (1 << 30)) ? BSX_ERANGE : 0;
+  if (rc == 0) rc = bsx_check_gumbel_call(call, policy, inv_temperature, state, steps, out, actions_out, info, cfg, 3);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_gumbel_args e;
+  mountain_car_env::args* a = &e.t.fam.mountain_car;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.t.out)
+  a->info = info; a->obs_numel = 3; a->max_steps = cfg->max_steps;
+  return bsx_gumbel_call(e, BSX_FAM_MOUNTAIN_CAR, call, policy, inv_temperature, out, actions_out);
+}
+
+extern "C" int bsx_mountain_car_linear_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                               double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                                               int32_t* actions_out, double* info) {
+  return mountain_car_sample(cfg, call, linear, inv_temperature, state, steps, out, actions_out, info);
+}
+
+extern "C" int bsx_mountain_car_mlp_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                            double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                                            int32_t* actions_out, double* info) {
+  return mountain_car_sample(cfg, call, mlp, inv_temperature, state, steps, out, actions_out, info);
 }
 
 extern "C" int bsx_group_set_mountain_car(bsx_group_t* g, int32_t index, const bsx_mountain_car_t* cfg, const bsx_call_t* call,

@@ -25,6 +25,7 @@ There is no CPU fallback: without a HIP device the first reset()/step() raises.
 import collections
 import contextlib
 import ctypes
+import math
 import secrets
 from typing import Any, Dict, Optional
 
@@ -1157,6 +1158,93 @@ class Environment(dm_env.EnvironmentBase):
     args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp)) + \
         tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
     self._launch_steps(getattr(_native.lib, self._mlp_rollout_abi), args, T, what)
+    return timestep, actions
+
+  _linear_sample_abi = None    # subclass: the C-ABI entry points of sample_linear / sample_mlp (cartpole, swing-up,
+  _mlp_sample_abi = None       # mountain_car)
+
+  @staticmethod
+  def _check_sample(what, temperature, sample_seed):
+    """What only the sampling calls refuse (before any GPU use): the temperature and the seed.  Returns beta = 1 / temperature,
+    computed here in float64: the kernel multiplies by it and never divides."""
+    ok = not isinstance(temperature, bool) and isinstance(temperature, (int, float, np.integer, np.floating))
+    t = float(temperature) if ok else float('nan')
+    ok = ok and math.isfinite(t) and t > 0.0
+    beta = 1.0 / t if ok else float('nan')
+    if not ok or not math.isfinite(beta):
+      raise ValueError(f'{what}: temperature must be a finite number > 0 with a finite 1 / temperature, got {temperature!r} '
+                       '(there is no greedy limit: that is rollout_linear / rollout_mlp)')
+    if isinstance(sample_seed, bool) or not isinstance(sample_seed, (int, np.integer)) or not 0 <= int(sample_seed) < (1 << 64):
+      raise ValueError(f'{what}: sample_seed must be an integer in [0, 2^64), got {sample_seed!r}')
+    return beta
+
+  def sample_linear(self, weights, observation, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`rollout_linear` for a learner that needs actions DRAWN from its policy (REINFORCE, actor-critic, PPO): the closed loop
+    of a linear softmax agent in ONE launch that writes the trajectory (Cartpole, CartpoleSwingup and MountainCar, batched
+    view, counter-based draws, no wrapper).  Returns `(ts, actions)` as rollout_linear does: `ts` with step_type int8 [T,B],
+    reward / discount float32 [T,B], observation float32 [T,B,*obs_shape], and `actions` int32 [T,B], the action drawn at
+    every step, 0 where the lane resets.  The call equals, bit for bit in everything it returns and everything it leaves
+    behind,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(linear_logits(weights[row], obs), words(sample_seed, lane, call index), temperature)
+                           ts[t] = step(a); actions[t] = a; obs = ts[t].observation
+
+    so `rollout(actions)` on a twin reproduces `ts`.  linear_logits and gumbel_select are utils.observations': the float32
+    logits of linear_select, then Gumbel-max in float64 — u_a = (word_a + 0.5) * 2^-32, g_a = -log(-log(u_a)) with the
+    engine's bit-reproducible logarithm, z_a = l_a * (1 / temperature) + g_a, the largest z wins, the lowest index wins a
+    tie, a NaN never wins — which draws action a with probability softmax(logits / temperature)[a].  The words are words
+    0..2 of stream 3 of (sample_seed, global lane id, call index): an epsilon-greedy call with the same seed shares none, and
+    nothing is drawn on a step that resets.  temperature: a finite number > 0 whose inverse is finite; there is no epsilon
+    (the softmax explores) and no greedy limit (rollout_linear).  weights, observation and policy_index are rollout_linear's:
+    the same shapes and population form, policy_index clamped to [0, P-1], and a lane that resets on the first step never
+    reads its row of `observation`.  Logits and log-probabilities are not outputs: a learner recomputes them from
+    `ts.observation` and `actions` with linear_logits.  State, bsuite_info(), episode_counters() and the call index are left
+    as T step() calls leave them; calls interleave freely with step / rollout / rollout_linear / rollout_mlp / evaluate_* /
+    mark_reset / reset.  Output buffers are cached per T, shared with rollout_linear(), rollout_mlp() and sample_mlp(), and
+    overwritten by the next call of the same T."""
+    what = 'sample_linear'
+    P = self._check_evaluate_linear(weights, observation, num_steps, policy_index, 0.0, 0, what=what, abi='_linear_sample_abi')
+    beta = self._check_sample(what, temperature, sample_seed)
+    self._check_trajectory_slab(what)
+    self._ensure_allocated()
+    T = int(num_steps)
+    _, ptrs, timestep, actions = self._trajectory_out(T)
+    lin = _native.Linear(weights.data_ptr(), P, policy_index.data_ptr() if policy_index is not None else None, 0.0,
+                         int(sample_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(lin), beta) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._linear_sample_abi), args, T, what)
+    return timestep, actions
+
+  def sample_mlp(self, w1, w2, observation, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`sample_linear` for an agent with one ReLU hidden layer — `rollout_mlp` with actions drawn from the softmax of its
+    logits: the same ONE launch, the same `(ts, actions)`, contract and refusals.  The call equals, bit for bit in everything
+    it returns and everything it leaves behind,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(mlp_logits(w1[row], w2[row], obs), words(sample_seed, lane, call index), temperature)
+                           ts[t] = step(a); actions[t] = a; obs = ts[t].observation
+
+    w1: float32 device tensor [H, D+1] or [P, H, D+1]; w2: [3, H+1] or [P, 3, H+1], 1 <= H <= 64; `policy_index` and
+    `observation` as in rollout_mlp; temperature and sample_seed as in sample_linear (utils.observations.mlp_logits and
+    gumbel_select have the rule).  A shared pair is kept on chip; a population is read from device memory by every lane on
+    every step: group the lanes by policy.  `rollout(actions)` on a twin reproduces `ts`.  Output buffers are cached per T,
+    shared with sample_linear() and the rollout_* calls, and overwritten by the next call of the same T."""
+    what = 'sample_mlp'
+    P, H = self._check_evaluate_mlp(w1, w2, observation, num_steps, policy_index, 0.0, 0, what=what, abi='_mlp_sample_abi')
+    beta = self._check_sample(what, temperature, sample_seed)
+    self._check_trajectory_slab(what)
+    self._ensure_allocated()
+    T = int(num_steps)
+    _, ptrs, timestep, actions = self._trajectory_out(T)
+    mlp = _native.Mlp(w1.data_ptr(), w2.data_ptr(), H, P, policy_index.data_ptr() if policy_index is not None else None,
+                      0.0, int(sample_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp), beta) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp_sample_abi), args, T, what)
     return timestep, actions
 
   def _step(self, action):

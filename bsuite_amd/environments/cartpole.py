@@ -74,6 +74,8 @@ class _CartpoleBase(base.Environment):
   _mlp_eval_abi = 'bsx_cartpole_mlp_evaluate'
   _linear_rollout_abi = 'bsx_cartpole_linear_rollout'
   _mlp_rollout_abi = 'bsx_cartpole_mlp_rollout'
+  _linear_sample_abi = 'bsx_cartpole_linear_sample'
+  _mlp_sample_abi = 'bsx_cartpole_mlp_sample'
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

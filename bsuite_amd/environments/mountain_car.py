@@ -32,6 +32,8 @@ class MountainCar(base.Environment):
   _mlp_eval_abi = 'bsx_mountain_car_mlp_evaluate'
   _linear_rollout_abi = 'bsx_mountain_car_linear_rollout'
   _mlp_rollout_abi = 'bsx_mountain_car_mlp_rollout'
+  _linear_sample_abi = 'bsx_mountain_car_linear_sample'
+  _mlp_sample_abi = 'bsx_mountain_car_mlp_sample'
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

@@ -1,5 +1,5 @@
 """Helpers for index observations (observation_mode='index' of deep_sea and catch) and for linear and hidden-layer policies on
-the float observations of the physics families (`env.evaluate_linear`, `env.evaluate_mlp`).
+the float observations of the physics families (`env.evaluate_linear`, `env.evaluate_mlp`, `env.sample_linear`, `env.sample_mlp`).
 
 An index observation names the hot cells of a one-hot board: int32 `[..., K]`, each entry a flat cell number of the
 dense board (`env.board_shape`) or -1 for "no cell" (deep_sea's all-zero terminal board).  Pure torch: they work on
@@ -7,6 +7,7 @@ any device and on any leading dimensions (`[B, K]` from step(), `[T, B, K]` from
 """
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 
@@ -120,3 +121,102 @@ def mlp_select(w1: torch.Tensor, w2: torch.Tensor, obs: torch.Tensor, return_pre
     best = torch.where(better, torch.full_like(best, a), best)
     l_best = torch.where(better, logits[:, a], l_best)
   return (best, s) if return_preactivations else best
+
+
+def linear_logits(weights: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
+  """The logits `[B, A]` (float32) of a linear policy on float observations, exactly as `env.sample_linear` computes them
+  inside its kernel (bsx_linear_logits, csrc/bsx_gumbel.h) — the accumulations of `linear_select`, without its argmax:
+
+    l_a = w[a][D]; for d = 0..D-1: l_a = l_a + w[a][d] * obs[d]        float32, every multiply and every add rounded on its
+                                                                       own: separate torch ops, never addcmul or matmul
+
+  `weights` is float32 `[A, D+1]` or `[B, A, D+1]` (lane b's own matrix), `obs` float32 `[B, *obs_shape]`.  What a learner
+  recomputes log-probabilities from: the action of step t was drawn from
+  `softmax(linear_logits(w, ts.observation[t - 1]) / temperature)`."""
+  o = obs.reshape(obs.shape[0], -1)
+  D = int(o.shape[1])
+  w = weights if weights.dim() == 3 else weights.unsqueeze(0).expand(o.shape[0], -1, -1)
+  logits = w[:, :, D].clone()
+  for d in range(D):
+    prod = w[:, :, d] * o[:, d:d + 1]
+    logits = logits + prod
+  return logits
+
+
+def mlp_logits(w1: torch.Tensor, w2: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
+  """The logits `[B, 3]` (float32) of a policy with one ReLU hidden layer, exactly as `env.sample_mlp` computes them inside its
+  kernel (csrc/bsx_mlp.h's pieces) — the accumulations of `mlp_select`, without its argmax:
+
+    l_a = w2[a][H]
+    for j = 0..H-1: s = w1[j][D]; for d = 0..D-1: s = s + w1[j][d] * obs[d]      float32, every multiply and every add rounded
+                    h = s if s > 0 else +0.0                                      on its own: separate torch ops, never addcmul
+                    l_a = l_a + w2[a][j] * h                                      or matmul; a NaN s gives h = 0
+
+  `w1` is float32 `[H, D+1]` and `w2` `[3, H+1]`, or `[B, H, D+1]` and `[B, 3, H+1]` (lane b's own pair)."""
+  o = obs.reshape(obs.shape[0], -1)
+  B, D = int(o.shape[0]), int(o.shape[1])
+  a1 = w1 if w1.dim() == 3 else w1.unsqueeze(0).expand(B, -1, -1)
+  a2 = w2 if w2.dim() == 3 else w2.unsqueeze(0).expand(B, -1, -1)
+  H = int(a1.shape[1])
+  s = a1[:, :, D].clone()
+  for d in range(D):
+    prod = a1[:, :, d] * o[:, d:d + 1]
+    s = s + prod
+  h = torch.where(s > 0, s, torch.zeros_like(s))
+  logits = a2[:, :, H].clone()
+  for j in range(H):
+    prod = a2[:, :, j] * h[:, j:j + 1]
+    logits = logits + prod
+  return logits
+
+
+def _stream_log(x: torch.Tensor) -> torch.Tensor:
+  """bsx_log (include/bsx_stream.h) on a float64 tensor of positive normal numbers, operation for operation: the exponent
+  and the mantissa from the bits, m in [~0.707, 1.414], s = (m - 1) / (m + 1), the odd series of 2 atanh(s) to s^25 by
+  Horner's rule with every multiply and every add a torch op of its own.  Never torch.log: its last bits differ."""
+  u = x.contiguous().view(torch.int64)
+  e = ((u >> 52) & 0x7FF) - 1023
+  m = ((u & 0x000FFFFFFFFFFFFF) | 0x3FF0000000000000).view(torch.float64)
+  big = m > 1.4142135623730951
+  m = torch.where(big, m * 0.5, m)
+  e = torch.where(big, e + 1, e)
+  s = (m - 1.0) / (m + 1.0)
+  s2 = s * s
+  p = torch.full_like(s, 1.0 / 25.0)
+  for d in (23.0, 21.0, 19.0, 17.0, 15.0, 13.0, 11.0, 9.0, 7.0, 5.0, 3.0):
+    p = p * s2
+    p = p + 1.0 / d
+  p = p * s2
+  p = p + 1.0
+  lm = (2.0 * s) * p
+  return e.to(torch.float64) * 0.6931471805599453 + lm
+
+
+def gumbel_select(logits: torch.Tensor, words, temperature: float = 1.0) -> torch.Tensor:
+  """The action `[B]` (int32) that `env.sample_linear` / `env.sample_mlp` draw from float32 `logits` `[B, 3]` and the lane's
+  three 32-bit words `[B, 3]` (a uint32 numpy array such as oracle.stream.words(sample_seed, lanes, call index, 3, 3), or an
+  integer tensor with values in [0, 2^32)), exactly as the kernel does (bsx_gumbel_select, csrc/bsx_gumbel.h) — Gumbel-max
+  in float64, every operation a torch op of its own:
+
+    beta = 1 / temperature                                   Python float64
+    u_a = (word_a + 0.5) * 2^-32                             exact, in (0, 1)
+    g_a = -log(-log(u_a))                                    the engine's bit-reproducible log, never torch.log
+    z_a = float64(l_a) * beta + g_a                          a multiply, then an add
+    best = 0; for a = 1, 2: if z_a > z_best: best = a        the lowest index wins a tie, a NaN never wins
+
+  so that P(a) = softmax(logits / temperature)[a] over the words."""
+  beta = 1.0 / float(temperature)
+  if not torch.is_tensor(words):
+    words = torch.from_numpy(np.ascontiguousarray(np.asarray(words).astype(np.int64)))
+  w = (words.to(torch.int64) & 0xFFFFFFFF).to(logits.device)
+  u = (w.to(torch.float64) + 0.5) * 2.0 ** -32
+  g = -_stream_log(-_stream_log(u))
+  z = logits.to(torch.float64) * beta
+  z = z + g
+  best = torch.zeros(z.shape[0], dtype=torch.int32, device=z.device)
+  z_best = z[:, 0]
+  for a in range(1, int(z.shape[1])):
+    better = z[:, a] > z_best
+    best = torch.where(better, torch.full_like(best, a), best)
+    z_best = torch.where(better, z[:, a], z_best)
+  return best

@@ -102,6 +102,18 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'rollout_mlp() is not available through {type(self).__name__}: the fused hidden-layer rollout has no '
                      'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
+  def sample_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused, like rollout_linear: the sampled trajectory records the raw environment's rewards (base.Environment.sample_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError(f'sample_linear() is not available through {type(self).__name__}: the fused sampled rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def sample_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused, like rollout_mlp: the sampled trajectory records the raw environment's rewards (base.Environment.sample_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError(f'sample_mlp() is not available through {type(self).__name__}: the fused sampled hidden-layer rollout has '
+                     'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -546,6 +558,18 @@ class ImageObservation(dm_env.EnvironmentBase):
     del w1, w2, observation, num_steps, kwargs
     raise ValueError('rollout_mlp() is not available through ImageObservation: the fused hidden-layer rollout selects its actions '
                      'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def sample_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused: the sampled linear rollout returns the raw environment's float rows, never images (base.Environment.sample_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError('sample_linear() is not available through ImageObservation: the fused sampled rollout draws its actions '
+                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def sample_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused: the sampled hidden-layer rollout returns the raw environment's float rows, never images (base.Environment.sample_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError('sample_mlp() is not available through ImageObservation: the fused sampled hidden-layer rollout draws its '
+                     'actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

@@ -524,6 +524,33 @@ int bsx_cartpole_mlp_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, 
 int bsx_mountain_car_mlp_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
                                  float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
 
+/* ---- fused sampled trajectories: the recording calls above with a softmax policy (cartpole, swing-up, mountain_car; v12,
+ *      additive) --------------------------------------------------------------------------------
+ * bsx_<family>_linear_rollout / bsx_<family>_mlp_rollout with the same policy struct, outputs, reset rule and refusals, in
+ * ONE launch — but the action of a lane that does not reset is a draw from softmax(inv_temperature * logits) instead of
+ * the greedy one.  The logits are exactly the float32 accumulations of the greedy rule (csrc/bsx_linear.h, csrc/bsx_mlp.h);
+ * the draw is Gumbel-max in float64 (csrc/bsx_gumbel.h), each operation rounded on its own:
+ *     u_a = ((double)word_a + 0.5) * 2^-32;  g_a = -bsx_log(-bsx_log(u_a));  z_a = (double)l_a * inv_temperature + g_a
+ *     argmax_a z_a, the lowest index wins a tie and a NaN never wins
+ * with word_a = word a of block 0 of stream 3 (BSX_STREAM_SAMPLE) of (explore_seed, global lane id, call index): the
+ * policy struct's explore_seed is the SAMPLE SEED of these calls.  A lane that resets takes action 0 and draws nothing.
+ * actions_out holds the actions drawn; bsx_<family>_step with n_steps and actions_out as its actions reproduces `out`.
+ * There is no greedy limit and no epsilon: BSX_ERANGE — where the recording calls refuse an epsilon outside [0, 1] — if
+ * the struct's epsilon is not 0.0 or inv_temperature is not a finite number > 0.  Every other refusal, and their order,
+ * is that of the recording calls, the 4 GiB slab included. */
+int bsx_cartpole_linear_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                               double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                               int32_t* actions_out, double* info);
+int bsx_mountain_car_linear_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                   double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                                   int32_t* actions_out, double* info);
+int bsx_cartpole_mlp_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                            double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                            int32_t* actions_out, double* info);
+int bsx_mountain_car_mlp_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                                int32_t* actions_out, double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */

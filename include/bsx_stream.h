@@ -20,6 +20,10 @@
  *               environment's seed, and a (lane, step) triple uses block 0 only: U() — words 0, 1 — and, if
  *               U < epsilon, RandInt(num_actions) — word 2.  Nothing is drawn by a lane that resets on that
  *               call, nor when epsilon == 0; streams 0 and 1 never depend on it.
+ *               3 = the Gumbel draws of a softmax policy inside a fused sampled trajectory
+ *               (bsx_<family>_linear_sample / bsx_<family>_mlp_sample); its key is the caller's sample seed and a
+ *               (lane, step) triple uses words 0..2 of block 0, word a for action a (csrc/bsx_gumbel.h).  Nothing is
+ *               drawn by a lane that resets on that call; an epsilon-greedy call with the same seed shares no word.
  *   draws consume words in order:
  *     U()        2 words a,b : k = (a>>5)<<26 | (b>>6) ; U = k * 2^-53   (numpy legacy rand())
  *     Bern()     1 word      : word >> 31                                 (binomial(1, .5))
@@ -50,6 +54,7 @@
 #define BSX_STREAM_ENV 0u
 #define BSX_STREAM_WRAP 1u
 #define BSX_STREAM_POLICY 2u
+#define BSX_STREAM_SAMPLE 3u
 
 typedef struct { uint32_t v[4]; } bsx_u32x4;
 
