@@ -111,6 +111,13 @@ class Policy(ctypes.Structure):
               ('actions_out', ctypes.c_void_p)]
 
 
+class PolicyLogits(ctypes.Structure):
+  """bsx_policy_logits_t: the table of logits of bsx_<family>_policy_sample / bsx_<family>_policy_sample_evaluate."""
+  _fields_ = [('logits', ctypes.c_void_p), ('n_states', ctypes.c_int32), ('n_actions', ctypes.c_int32),
+              ('n_policies', ctypes.c_int32), ('policy_index', ctypes.c_void_p), ('inv_temperature', ctypes.c_double),
+              ('sample_seed', ctypes.c_uint64), ('actions_out', ctypes.c_void_p)]
+
+
 class PolicyEvalPtrs(ctypes.Structure):
   """bsx_policy_eval_t: the three output columns of bsx_<family>_policy_evaluate."""
   _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p)]
@@ -220,6 +227,15 @@ _SIGS = {
                                       PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_catch_policy_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
                                    PolicyEvalPtrs, _P], ctypes.c_int),
+    # sample_policy / evaluate_sampled_policy: the signatures of *_policy_rollout / *_policy_evaluate with a table of logits
+    'bsx_deep_sea_policy_sample': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
+                                    TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_catch_policy_sample': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
+                                 TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_deep_sea_policy_sample_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
+                                             PolicyEvalPtrs, _P], ctypes.c_int),
+    'bsx_catch_policy_sample_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
+                                          PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_bandit_step': ([ctypes.POINTER(BanditCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                         ctypes.c_int),
     'bsx_memory_chain_step': ([ctypes.POINTER(MemoryChainCfg), ctypes.POINTER(Call), _P, _P, _P,

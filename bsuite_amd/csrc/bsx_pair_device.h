@@ -104,14 +104,8 @@ __global__ void __launch_bounds__(BSX_BLOCK) bsx_advance2_kernel(const typename 
   bsx_advance_body<Fam, true, -1, 2>(a, blockIdx.x, s_fam, s_cnt);
 }
 
-template <class Fam>
-__global__ void __launch_bounds__(BSX_BLOCK) bsx_advance_group_kernel(const typename Fam::args* __restrict__ table,
-                                                                      const bsx_group_index gi) {
-  __shared__ typename Fam::shared s_fam;
-  __shared__ unsigned int s_cnt[2];
-  const bsx_group_slot w = bsx_group_find(gi, (int)blockIdx.x);
-  bsx_advance_body<Fam>(table[w.seg], w.block, s_fam, s_cnt);
-}
+// (the lane advance of a single-family GROUP — bsx_advance_body<Fam> over a table of segments — is ONE kernel for deep_sea and
+// catch, the family a uniform switch: bsx_pair_advance_group_kernel, misc.hip)
 
 // ---------------------------------------------------------------------------------------------
 // Index observations (bsx_call_t.flags & BSX_CALL_OBS_INDEX): the observation of a lane is the K = HotFn::INDEX_K hot-cell

@@ -114,11 +114,13 @@ static inline int bsx_group_put_pair(bsx_group* g, int32_t index, const typename
   return 0;
 }
 
+// Launches bsx_pair_advance_group_kernel (misc.hip): the lane advance of every segment of a single-family group of `family`
+// (BSX_FAM_DEEP_SEA / BSX_FAM_CATCH), `table` the device array of the family's args, one workgroup per 256 lanes.
+void bsx_launch_pair_advance_group(int32_t family, const void* table, const bsx_group_index& gi, int64_t total_blocks, hipStream_t st);
+
 template <class Fam, class HotFn, int K>
 static int bsx_group_launch_pair(bsx_group* g, int phase, hipStream_t st) {
-  if (phase != 1)
-    bsx_advance_group_kernel<Fam><<<dim3((unsigned)g->total_blocks), dim3(BSX_BLOCK), 0, st>>>(
-        (const typename Fam::args*)g->d_args, g->index1());
+  if (phase != 1) bsx_launch_pair_advance_group(HotFn::FAMILY, g->d_args, g->index1(), g->total_blocks, st);
   if (phase != 0)
     bsx_hot_stream_group_kernel<HotFn, K><<<dim3((unsigned)g->total_blocks2), dim3(BSX_BLOCK), 0, st>>>(
         (const bsx_stream_seg<HotFn>*)g->d_args2, g->index2());

@@ -17,6 +17,7 @@
 // state) measured 5.1-5.5 TB/s against 6.2-6.4 TB/s for this pair (profiles/r01/ab_*.log).
 #include "bsx_pair_host.h"
 #include "bsx_tab_eval.h"
+#include "bsx_tab_sample_device.h"
 #include "deep_sea_fam.h"
 #include "pair_mixed.h"
 
@@ -222,6 +223,32 @@ extern "C" int bsx_deep_sea_policy_evaluate(const bsx_deep_sea_t* cfg, const bsx
   bsx_tab_eval_args e;
   deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &e.fam.deep_sea);     // (no action column, no TimeStep)
   return bsx_tab_eval_call(e, BSX_FAM_DEEP_SEA, call, policy, 2u, out);
+}
+
+extern "C" int bsx_deep_sea_policy_sample(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                                          int32_t* state, bsx_timestep_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_tab_softmax_call(call, policy, bsx_policy_states_deep_sea(cfg->size), 2, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_tab_softmax_args s;
+  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_deep_sea_policy_rollout)
+  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &s.fam.deep_sea);
+  if (rc != 0) return rc;
+  s.fam.deep_sea.action = nullptr;
+  return bsx_tab_softmax_call(s, BSX_FAM_DEEP_SEA, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+}
+
+extern "C" int bsx_deep_sea_policy_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call,
+                                                   const bsx_policy_logits_t* policy, int32_t* state, bsx_policy_eval_t out,
+                                                   double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_tab_softmax_eval_call(call, policy, bsx_policy_states_deep_sea(cfg->size), 2, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_tab_softmax_args s;
+  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);     // (no action column, no TimeStep)
+  return bsx_tab_softmax_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
 }
 
 extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_deep_sea_t* cfg,

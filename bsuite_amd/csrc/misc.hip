@@ -101,6 +101,33 @@ int bsx_launch_tab_eval(const bsx_tab_eval_args& a, hipStream_t st) {
   return bsx_launch_status();
 }
 
+// The lane advance of a single-family group (bsx_group_set_deep_sea / bsx_group_set_catch on a group of that family;
+// bsx_group_launch_pair, phase 0): ONE kernel for deep_sea and catch, off every measured path.  The family is a uniform switch
+// — `table` is the device array of that family's args, one per segment — and each branch is bsx_advance_body<Fam>
+// (bsx_pair_device.h) on the segment and the block bsx_group_find names.
+struct bsx_pair_advance_group_args {
+  const void* table;
+  bsx_group_index gi;
+  int32_t family;
+};
+
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_pair_advance_group_kernel(const bsx_pair_advance_group_args a) {
+  __shared__ deep_sea_fam::shared s_deep_sea;
+  __shared__ catch_fam::shared s_catch;
+  __shared__ unsigned int s_cnt[2];
+  const bsx_group_slot w = bsx_group_find(a.gi, (int)blockIdx.x);
+  if (a.family == BSX_FAM_DEEP_SEA)
+    bsx_advance_body<deep_sea_fam>(static_cast<const deep_sea_fam::args*>(a.table)[w.seg], w.block, s_deep_sea, s_cnt);
+  else
+    bsx_advance_body<catch_fam>(static_cast<const catch_fam::args*>(a.table)[w.seg], w.block, s_catch, s_cnt);
+}
+
+void bsx_launch_pair_advance_group(int32_t family, const void* table, const bsx_group_index& gi, int64_t total_blocks, hipStream_t st) {
+  bsx_pair_advance_group_args a;
+  a.table = table; a.gi = gi; a.family = family;
+  bsx_pair_advance_group_kernel<<<dim3((unsigned)total_blocks), dim3(BSX_BLOCK), 0, st>>>(a);
+}
+
 extern "C" const char* bsx_strerror(int code) {
   switch (code) {
     case 0: return "ok";

@@ -817,10 +817,11 @@ class Environment(dm_env.EnvironmentBase):
     """Entries of one table of `rollout_policy` (deep_sea: N * N, catch: rows * columns * columns)."""
     raise ValueError(f'{type(self).__name__} has no tabular policy rollout (deep_sea and catch only)')
 
-  def _check_rollout_policy(self, policy, num_steps, policy_index, epsilon, explore_seed, what='rollout_policy'):
-    """The refusals of rollout_policy() and evaluate_policy() (`what`): all of them before any GPU use, nothing allocated."""
+  def _check_policy_env(self, what, num_steps, abi='_policy_abi'):
+    """The environment's part of the refusals of the fused tabular calls (`what`; `abi`: the attribute that names its entry
+    point): the family, the view, the modes and num_steps.  Before any GPU use, nothing allocated."""
     name = type(self).__name__
-    if self._policy_abi is None:
+    if getattr(self, abi) is None:
       raise ValueError(f'{name} has no tabular policy rollout (deep_sea and catch only)')
     if self._scalar:
       raise ValueError(f'{what}() needs the batched view (batch=B)')
@@ -837,6 +838,21 @@ class Environment(dm_env.EnvironmentBase):
       raise RuntimeError(f'{what}() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
     if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
       raise ValueError(f'{what}: num_steps must be an integer >= 1, got {num_steps!r}')
+
+  def _check_policy_population(self, what, P, policy_index):
+    """... and the rule both kinds of table share: `policy_index` names each lane's row of a population of P tables."""
+    if P == 1:
+      if policy_index is not None:
+        raise ValueError(f'{what}: policy_index names the row of a population of tables; with one table it must be None')
+    elif (not torch.is_tensor(policy_index) or policy_index.dtype != torch.int32 or policy_index.device != self._device
+          or tuple(policy_index.shape) != (self._batch,) or not policy_index.is_contiguous()):
+      raise ValueError(f'{what}: a population of {P} tables needs policy_index, a contiguous int32 tensor of shape '
+                       f'({self._batch},) on {self._device}')
+
+  def _check_rollout_policy(self, policy, num_steps, policy_index, epsilon, explore_seed, what='rollout_policy'):
+    """The refusals of rollout_policy() and evaluate_policy() (`what`): all of them before any GPU use, nothing allocated.
+    The environment's part (_check_policy_env), then the table of actions' own."""
+    self._check_policy_env(what, num_steps)
     if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
       raise ValueError(f'{what}: epsilon must be a number in [0, 1], got {epsilon!r}')
     if isinstance(explore_seed, bool) or not isinstance(explore_seed, (int, np.integer)) or not 0 <= int(explore_seed) < (1 << 64):
@@ -846,14 +862,20 @@ class Environment(dm_env.EnvironmentBase):
         or int(policy.shape[-1]) != S or policy.numel() == 0 or not policy.is_contiguous()):
       raise ValueError(f'{what}: policy must be a contiguous uint8 tensor of shape ({S},) or (P, {S}) on {self._device}')
     P = 1 if policy.dim() == 1 else int(policy.shape[0])
-    if P == 1:
-      if policy_index is not None:
-        raise ValueError(f'{what}: policy_index names the row of a population of tables; with one table it must be None')
-    elif (not torch.is_tensor(policy_index) or policy_index.dtype != torch.int32 or policy_index.device != self._device
-          or tuple(policy_index.shape) != (self._batch,) or not policy_index.is_contiguous()):
-      raise ValueError(f'{what}: a population of {P} tables needs policy_index, a contiguous int32 tensor of shape '
-                       f'({self._batch},) on {self._device}')
+    self._check_policy_population(what, P, policy_index)
     return P
+
+  def _check_sample_policy(self, logits, num_steps, policy_index, temperature, sample_seed, what, abi):
+    """The refusals of sample_policy() and evaluate_sampled_policy() (`what`), all before any GPU use: the environment's part,
+    the table of logits, then the temperature and the seed (_check_sample).  Returns (P, beta)."""
+    self._check_policy_env(what, num_steps, abi=abi)
+    S, A = self.policy_num_states, int(self._num_actions)
+    if (not torch.is_tensor(logits) or logits.dtype != torch.float32 or logits.device != self._device or logits.dim() not in (2, 3)
+        or tuple(logits.shape[-2:]) != (S, A) or logits.numel() == 0 or not logits.is_contiguous()):
+      raise ValueError(f'{what}: logits must be a contiguous float32 tensor of shape ({S}, {A}) or (P, {S}, {A}) on {self._device}')
+    P = 1 if logits.dim() == 2 else int(logits.shape[0])
+    self._check_policy_population(what, P, policy_index)
+    return P, self._check_sample(what, temperature, sample_seed)
 
   def rollout_policy(self, policy, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
     """A closed-loop rollout of `num_steps` steps in ONE launch, the actions looked up in a table by the lane's own
@@ -891,6 +913,15 @@ class Environment(dm_env.EnvironmentBase):
 
   _policy_eval_abi = None   # subclass: the C-ABI entry point of evaluate_policy (deep_sea, catch)
 
+  def _policy_evaluation_out(self):
+    """The cached output columns of evaluate_policy() and evaluate_sampled_policy()."""
+    if self._policy_eval_out is None:
+      self._policy_eval_out = PolicyEvaluation(
+          episodes=torch.empty(self._batch, dtype=torch.int32, device=self._device),
+          return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
+          episode_return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device))
+    return self._policy_eval_out
+
   def evaluate_policy(self, policy, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
     """`rollout_policy` with the same arguments, returns only: the lanes take the same `num_steps` steps in ONE launch — same
     actions, draws, keys and clamps — and state, bsuite_info(), episode_counters(), invalid_action_count() and the call
@@ -914,18 +945,83 @@ class Environment(dm_env.EnvironmentBase):
     rollout_policy / mark_reset / reset."""
     P = self._check_rollout_policy(policy, num_steps, policy_index, epsilon, explore_seed, what='evaluate_policy')
     self._ensure_allocated()
-    if self._policy_eval_out is None:
-      self._policy_eval_out = PolicyEvaluation(
-          episodes=torch.empty(self._batch, dtype=torch.int32, device=self._device),
-          return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device),
-          episode_return_sum=torch.empty(self._batch, dtype=torch.float64, device=self._device))
-    ev = self._policy_eval_out
+    ev = self._policy_evaluation_out()
     pol = _native.Policy(policy.data_ptr(), self.policy_num_states, P,
                          policy_index.data_ptr() if policy_index is not None else None, float(epsilon), int(explore_seed), None)
     out = _native.PolicyEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr())
     args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), out,
             self._info.data_ptr())
     self._launch_steps(getattr(_native.lib, self._policy_eval_abi), args, int(num_steps), 'evaluate_policy')
+    return ev
+
+  _policy_sample_abi = None        # subclass: the C-ABI entry points of sample_policy / evaluate_sampled_policy (deep_sea,
+  _policy_sample_eval_abi = None   # catch)
+
+  def _policy_logits(self, logits, P, policy_index, beta, sample_seed, actions):
+    return _native.PolicyLogits(logits.data_ptr(), self.policy_num_states, int(self._num_actions), P,
+                                policy_index.data_ptr() if policy_index is not None else None, beta, int(sample_seed),
+                                actions.data_ptr() if actions is not None else None)
+
+  def sample_policy(self, logits, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`rollout_policy` for a learner whose tabular policy is a softmax (REINFORCE, actor-critic, softmax population search):
+    a closed-loop rollout of `num_steps` steps in ONE launch, the actions DRAWN from softmax(logits[row, key] / temperature)
+    (DeepSea and Catch, batched view, observation_mode='index', counter-based draws, no wrapper).
+
+    logits: a contiguous float32 device tensor [S, A] (one table for all lanes) or [P, S, A] (a population; `policy_index`,
+    int32 [B], names each lane's row and is clamped to [0, P-1]; with one table it must be None); S = `policy_num_states`,
+    A = action_spec().num_values (deep_sea 2, catch 3).  Only 4-byte alignment is assumed: a view that starts one float into
+    a buffer is fine.  Returns `(ts, actions)` as rollout_policy does — `ts` with step_type int8 / reward / discount float32
+    [T,B] and the int32 index observation [T,B,K], `actions` int32 [T,B] — and equals, bit for bit in everything it returns
+    and everything it leaves behind,
+
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(logits[row, key(observation before the call)], words(sample_seed, lane, call index),
+                                             temperature)
+                           ts[t] = step(a); actions[t] = a
+
+    key is utils.observations.policy_key (clamped into the table like rollout_policy's), gumbel_select is
+    utils.observations': Gumbel-max in float64 over the A logits — u_a = (word_a + 0.5) * 2^-32, g_a = -log(-log(u_a)) with the
+    engine's bit-reproducible logarithm, z_a = l_a * (1 / temperature) + g_a, the largest z wins, the lowest index wins a
+    tie, a NaN never wins and a -inf logit masks its action — which draws action a with probability
+    softmax(logits / temperature)[a].  The words are words 0..A-1 of block 0 of stream 3 of (sample_seed, global lane id, call
+    index); nothing is drawn on a step that resets, and the environment's own stream 0 is untouched, so `rollout(actions)` on
+    a twin reproduces `ts`.  temperature: a finite number > 0 whose inverse is finite; there is no epsilon and no greedy
+    limit (that is rollout_policy).  Log-probabilities are not outputs: a learner gathers `logits[row, key]` itself.  A shared
+    table of at most 12 KiB (every catch up to rows * columns^2 = 1024, deep_sea up to N = 39) is kept on chip; a larger one
+    and every population is read from device memory.  State, bsuite_info(), episode_counters(), invalid_action_count() and the
+    call index are left as T step() calls leave them; calls interleave freely with step / rollout / rollout_policy /
+    evaluate_policy / mark_reset / reset.  Output buffers are cached per T, shared with rollout_policy(), and overwritten by
+    the next call of the same T."""
+    what = 'sample_policy'
+    P, beta = self._check_sample_policy(logits, num_steps, policy_index, temperature, sample_seed, what, '_policy_sample_abi')
+    self._ensure_allocated()
+    T = int(num_steps)
+    if T not in self._policy_rollout_out:
+      actions = torch.empty((T, self._batch), dtype=torch.int32, device=self._device)
+      self._policy_rollout_out[T] = self._new_outputs((T, self._batch), dict(device=self._device)) + (actions,)
+    _, ptrs, timestep, actions = self._policy_rollout_out[T]
+    pol = self._policy_logits(logits, P, policy_index, beta, sample_seed, actions)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), ptrs,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._policy_sample_abi), args, T, what)
+    return timestep, actions
+
+  def evaluate_sampled_policy(self, logits, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`sample_policy` with the same arguments, returns only: the lanes take the same `num_steps` steps with the same draws in
+    ONE launch, and state, bsuite_info(), episode_counters(), invalid_action_count() and the call index are left bit for bit
+    where sample_policy leaves them, but no TimeStep is written.  Returns the cached `PolicyEvaluation` of evaluate_policy —
+    episodes int32, return_sum and episode_return_sum float64, [B] each — with the same definitions: the float64 reward of
+    the step before its rounding to float32, summed in step order (evaluate_policy has the loop).  The refusals are
+    sample_policy's.  The three buffers are shared with evaluate_policy() and overwritten by the next call of either."""
+    what = 'evaluate_sampled_policy'
+    P, beta = self._check_sample_policy(logits, num_steps, policy_index, temperature, sample_seed, what, '_policy_sample_eval_abi')
+    self._ensure_allocated()
+    ev = self._policy_evaluation_out()
+    pol = self._policy_logits(logits, P, policy_index, beta, sample_seed, None)
+    out = _native.PolicyEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), out,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._policy_sample_eval_abi), args, int(num_steps), what)
     return ev
 
   _linear_eval_abi = None   # subclass: the C-ABI entry point of evaluate_linear (cartpole, swing-up, mountain_car)

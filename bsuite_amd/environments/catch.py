@@ -47,6 +47,8 @@ class Catch(base.Environment):
 
   _policy_abi = 'bsx_catch_policy_rollout'
   _policy_eval_abi = 'bsx_catch_policy_evaluate'
+  _policy_sample_abi = 'bsx_catch_policy_sample'
+  _policy_sample_eval_abi = 'bsx_catch_policy_sample_evaluate'
 
   @property
   def policy_num_states(self) -> int:

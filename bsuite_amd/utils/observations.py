@@ -193,16 +193,17 @@ def _stream_log(x: torch.Tensor) -> torch.Tensor:
 
 
 def gumbel_select(logits: torch.Tensor, words, temperature: float = 1.0) -> torch.Tensor:
-  """The action `[B]` (int32) that `env.sample_linear` / `env.sample_mlp` draw from float32 `logits` `[B, 3]` and the lane's
-  three 32-bit words `[B, 3]` (a uint32 numpy array such as oracle.stream.words(sample_seed, lanes, call index, 3, 3), or an
-  integer tensor with values in [0, 2^32)), exactly as the kernel does (bsx_gumbel_select, csrc/bsx_gumbel.h) — Gumbel-max
-  in float64, every operation a torch op of its own:
+  """The action `[B]` (int32) that `env.sample_linear` / `env.sample_mlp` (A = 3) and `env.sample_policy` /
+  `env.evaluate_sampled_policy` (A = 2 for deep_sea, 3 for catch) draw from float32 `logits` `[B, A]` and the lane's A 32-bit
+  words `[B, A]` (a uint32 numpy array such as oracle.stream.words(sample_seed, lanes, call index, 3, A), or an integer tensor
+  with values in [0, 2^32)), exactly as the kernels do (bsx_gumbel_select, csrc/bsx_gumbel.h; bsx_gumbel_select_n,
+  csrc/bsx_tab_sample.h) — Gumbel-max in float64, every operation a torch op of its own:
 
     beta = 1 / temperature                                   Python float64
     u_a = (word_a + 0.5) * 2^-32                             exact, in (0, 1)
     g_a = -log(-log(u_a))                                    the engine's bit-reproducible log, never torch.log
     z_a = float64(l_a) * beta + g_a                          a multiply, then an add
-    best = 0; for a = 1, 2: if z_a > z_best: best = a        the lowest index wins a tie, a NaN never wins
+    best = 0; for a = 1 .. A-1: if z_a > z_best: best = a    the lowest index wins a tie, a NaN never wins
 
   so that P(a) = softmax(logits / temperature)[a] over the words."""
   beta = 1.0 / float(temperature)

@@ -114,6 +114,19 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'sample_mlp() is not available through {type(self).__name__}: the fused sampled hidden-layer rollout has '
                      'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
+  def sample_policy(self, logits, num_steps, **kwargs):
+    """Refused, like rollout_policy: the sampled rollout records the raw environment's rewards (base.Environment.sample_policy)."""
+    del logits, num_steps, kwargs
+    raise ValueError(f'sample_policy() is not available through {type(self).__name__}: the fused sampled policy rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_sampled_policy(self, logits, num_steps, **kwargs):
+    """Refused, like evaluate_policy: the sampled evaluation sums the raw environment's rewards
+    (base.Environment.evaluate_sampled_policy)."""
+    del logits, num_steps, kwargs
+    raise ValueError(f'evaluate_sampled_policy() is not available through {type(self).__name__}: the fused sampled policy '
+                     'evaluation has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -570,6 +583,20 @@ class ImageObservation(dm_env.EnvironmentBase):
     del w1, w2, observation, num_steps, kwargs
     raise ValueError('sample_mlp() is not available through ImageObservation: the fused sampled hidden-layer rollout draws its '
                      'actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def sample_policy(self, logits, num_steps, **kwargs):
+    """Refused, like rollout_policy: a fused sampled policy rollout returns index observations, never images
+    (base.Environment.sample_policy)."""
+    del logits, num_steps, kwargs
+    raise ValueError('sample_policy() is not available through ImageObservation: the fused sampled policy rollout returns index '
+                     'observations; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_sampled_policy(self, logits, num_steps, **kwargs):
+    """Refused, like evaluate_policy: the fused sampled evaluation looks its logits up by index observations
+    (base.Environment.evaluate_sampled_policy)."""
+    del logits, num_steps, kwargs
+    raise ValueError('evaluate_sampled_policy() is not available through ImageObservation: the fused sampled policy evaluation '
+                     'looks its logits up by index observations; call it on an un-wrapped DeepSea / Catch')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

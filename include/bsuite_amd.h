@@ -344,6 +344,46 @@ int bsx_deep_sea_policy_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* ca
 int bsx_catch_policy_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
                               int32_t* state, bsx_policy_eval_t out, double* info);
 
+/* ---- fused sampled rollouts from a table of logits (deep_sea, catch; v12, additive) -------------
+ * bsx_<family>_policy_rollout / bsx_<family>_policy_evaluate with another action source, in ONE launch: a table of float32
+ * logits [n_policies, n_states, n_actions] (n_actions: deep_sea 2, catch 3) instead of a table of actions, and a draw from
+ * softmax(inv_temperature * logits) instead of the entry (and no epsilon coin).  Per step t and lane i:
+ *     a = 0                                        if the lane resets on this call
+ *       = argmax_c z_c                             else, with l = logits + (row(i) * n_states + key) * n_actions,
+ *         u_c = ((double)word_c + 0.5) * 2^-32;  g_c = -bsx_log(-bsx_log(u_c));  z_c = (double)l[c] * inv_temperature + g_c
+ *         (float64, each operation rounded on its own; c = 0 .. n_actions-1 in order, the lowest index wins a tie, a NaN
+ *         never wins, a -inf logit masks its action: csrc/bsx_tab_sample.h, csrc/bsx_gumbel.h)
+ *     then exactly step(a).
+ * key, its clamp, row(i) and its clamp are those of bsx_<family>_policy_rollout; word_c = word c of block 0 of stream 3
+ * (BSX_STREAM_SAMPLE) of (sample_seed, global lane id, the step's call index).  A lane that resets draws nothing; the
+ * environment's own stream is untouched.
+ *   bsx_<family>_policy_sample            writes what bsx_<family>_policy_rollout writes: `out` [n_steps, n_lanes(, K)] and
+ *                                         actions_out[t * n_lanes + i] = a; bsx_<family>_step with actions_out reproduces `out`
+ *   bsx_<family>_policy_sample_evaluate   takes the same steps with the same draws and writes what bsx_<family>_policy_evaluate
+ *                                         writes: the three columns of bsx_policy_eval_t; actions_out is not looked at
+ * State, info, counters and the call index end up as n_steps step() calls leave them, the same after either call.
+ * Refusals (all before any device work), in the order of bsx_<family>_policy_rollout / _policy_evaluate: BSX_EMODE as there;
+ * BSX_EINVAL also for n_states or n_actions other than the family's; BSX_ERANGE for an inv_temperature that is not a
+ * finite number > 0 (where an epsilon outside [0, 1] is refused there); BSX_ENULL as there; and last BSX_EALIGN for logits
+ * that are not 4-byte aligned — no wider alignment is assumed.  n_lanes == 0 returns 0 and launches nothing.  Asynchronous
+ * on call->hip_stream, no allocation, no synchronisation, graph-capturable. */
+typedef struct {
+  const float*   logits;         /* device [n_policies, n_states, n_actions]                       */
+  int32_t        n_states, n_actions, n_policies;
+  const int32_t* policy_index;   /* device [n_lanes] or NULL when n_policies == 1                  */
+  double         inv_temperature;
+  uint64_t       sample_seed;
+  int32_t*       actions_out;    /* device [n_steps, n_lanes] (bsx_<family>_policy_sample)         */
+} bsx_policy_logits_t;
+int bsx_deep_sea_policy_sample(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                               int32_t* state, bsx_timestep_t out, double* info);
+int bsx_catch_policy_sample(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                            int32_t* state, bsx_timestep_t out, double* info);
+int bsx_deep_sea_policy_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                                        int32_t* state, bsx_policy_eval_t out, double* info);
+int bsx_catch_policy_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                                     int32_t* state, bsx_policy_eval_t out, double* info);
+
 /* ---- bandit : bsuite/environments/bandit.py:35-73 ----------------------------------------- */
 #define BSX_BANDIT_MAX_ACTIONS 32
 typedef struct {

@@ -24,6 +24,10 @@
  *               (bsx_<family>_linear_sample / bsx_<family>_mlp_sample); its key is the caller's sample seed and a
  *               (lane, step) triple uses words 0..2 of block 0, word a for action a (csrc/bsx_gumbel.h).  Nothing is
  *               drawn by a lane that resets on that call; an epsilon-greedy call with the same seed shares no word.
+ *               The fused sampled rollouts from a table of logits (bsx_<family>_policy_sample /
+ *               bsx_<family>_policy_sample_evaluate, sample_policy / evaluate_sampled_policy: deep_sea, catch) draw from
+ *               the same stream by the same rule: words 0..A-1 of block 0 for A = 2 or 3 actions
+ *               (csrc/bsx_tab_sample.h).
  *   draws consume words in order:
  *     U()        2 words a,b : k = (a>>5)<<26 | (b>>6) ; U = k * 2^-53   (numpy legacy rand())
  *     Bern()     1 word      : word >> 31                                 (binomial(1, .5))
