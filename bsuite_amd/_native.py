@@ -267,6 +267,9 @@ for _fam, _cfg in (('cartpole', CartpoleCfg), ('mountain_car', MountainCarCfg)):
     # sample_linear / sample_mlp: the recording call's arguments with `double inv_temperature` after the policy struct
     _SIGS[f'bsx_{_fam}_{_kind}_sample'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy), ctypes.c_double,
                                             _P, _P, TimeStepPtrs, _P, _P], ctypes.c_int)
+    # evaluate_sampled_linear / evaluate_sampled_mlp: the evaluation's arguments with `double inv_temperature` after the struct
+    _SIGS[f'bsx_{_fam}_{_kind}_sample_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy),
+                                                     ctypes.c_double, _P, _P, LinearEvalPtrs, _P], ctypes.c_int)
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({
     'bsx_group_create': ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_G)], ctypes.c_int),

@@ -683,11 +683,11 @@ __device__ __forceinline__ void bsx_patch_board(float* __restrict__ board, int32
   if (b1 >= 0 && b1 != a0 && b1 != b0) board[b1] = 1.0f;
 }
 
+// The body of bsx_pair_advance_delta_kernel (misc.hip), which serves both families: one lane per thread, the workgroup's
+// staging in `s_fam`.
 template <class Fam, class HotFn>
-__global__ void __launch_bounds__(BSX_BLOCK) bsx_advance_delta_kernel(const typename Fam::args a, const HotFn fn,
-                                                                      int32_t* __restrict__ paint, const uint32_t cells) {
-  __shared__ typename Fam::shared s_fam;
-  __shared__ unsigned int s_cnt[2];
+__device__ __forceinline__ void bsx_advance_delta_body(const typename Fam::args& a, const HotFn& fn, int32_t* __restrict__ paint,
+                                                       const uint32_t cells, typename Fam::shared& s_fam, unsigned int* s_cnt) {
   if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
   Fam::stage(a, s_fam);
   __syncthreads();

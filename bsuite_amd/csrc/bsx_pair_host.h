@@ -27,13 +27,18 @@ static inline int bsx_launch_advance(const typename Fam::args& a, hipStream_t st
   return 0;
 }
 
-// ... and of the delta observation mode (bsx_advance_delta_kernel).
+// ... and of the delta observation mode: bsx_pair_advance_delta_kernel (misc.hip), ONE kernel for deep_sea and catch.
+// `args` is the family's args and `fn` its decoder (BSX_FAM_DEEP_SEA: deep_sea_fam::args, deep_sea_hot; BSX_FAM_CATCH:
+// catch_fam::args, catch_hot), both copied into the launch.
+void bsx_launch_pair_advance_delta(int32_t family, const void* args, const void* fn, int32_t* paint, uint32_t cells, int64_t blocks,
+                                   hipStream_t st);
+
 template <class Fam, class HotFn>
 static inline int bsx_launch_advance_delta(const typename Fam::args& a, const HotFn& fn, int32_t* paint,
                                            uint32_t cells, hipStream_t st) {
   const int64_t blocks = bsx_blocks_of(a.ctl.n_lanes);
   if (blocks > 0x7FFFFFFF) return BSX_EINVAL;
-  bsx_advance_delta_kernel<Fam, HotFn><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(a, fn, paint, cells);
+  bsx_launch_pair_advance_delta(HotFn::FAMILY, &a, &fn, paint, cells, blocks, st);
   return 0;
 }
 

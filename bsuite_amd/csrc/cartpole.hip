@@ -7,6 +7,7 @@
 #include "bsx_mlp_returns.h"
 #include "bsx_trajectory.h"
 #include "bsx_gumbel_device.h"
+#include "bsx_drawn_returns.h"
 #include "cartpole_env.h"
 
 // The parameters derived from a cfg on the host in f64, rounded once; BSX_ERANGE for a cfg outside the family's range.
@@ -122,6 +123,33 @@ extern "C" int bsx_cartpole_linear_sample(const bsx_cartpole_t* cfg, const bsx_c
 extern "C" int bsx_cartpole_mlp_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, double inv_temperature,
                                         float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
   return cartpole_sample(cfg, call, mlp, inv_temperature, state, steps, out, actions_out, info);
+}
+
+// evaluate_sampled_linear / evaluate_sampled_mlp: the sampled closed loop, writing only what the evaluation writes.
+template <class Policy>
+static int cartpole_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const Policy* policy, double inv_temperature,
+                                    float* state, int32_t* steps, const bsx_linear_eval_t& out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  bsx_drawn_returns_args e;
+  cartpole_env::args* a = &e.fam.cartpole;
+  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
+  if (rc == 0) rc = bsx_check_drawn_returns_call(call, policy, inv_temperature, state, steps, out, info, cfg->time_frac);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
+  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+  return bsx_drawn_returns_call(e, BSX_FAM_CARTPOLE, call, policy, inv_temperature, out);
+}
+
+extern "C" int bsx_cartpole_linear_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                                    double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                                    double* info) {
+  return cartpole_sample_evaluate(cfg, call, linear, inv_temperature, state, steps, out, info);
+}
+
+extern "C" int bsx_cartpole_mlp_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                                 double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                                 double* info) {
+  return cartpole_sample_evaluate(cfg, call, mlp, inv_temperature, state, steps, out, info);
 }
 
 extern "C" int bsx_group_set_cartpole(bsx_group_t* g, int32_t index, const bsx_cartpole_t* cfg, const bsx_call_t* call,

@@ -128,6 +128,49 @@ void bsx_launch_pair_advance_group(int32_t family, const void* table, const bsx_
   bsx_pair_advance_group_kernel<<<dim3((unsigned)total_blocks), dim3(BSX_BLOCK), 0, st>>>(a);
 }
 
+// The lane advance of the delta observation mode (bsx_call_t.obs_paint; bsx_launch_advance_delta): ONE kernel for deep_sea
+// and catch, off every measured path.  The arguments are a tagged struct — `family` says which member of `fam` and of `fn`
+// is set — the family is a uniform switch, and each branch is bsx_advance_delta_body<Fam, HotFn> (bsx_pair_device.h).
+struct bsx_pair_advance_delta_args {
+  int32_t family;
+  uint32_t cells;
+  int32_t* paint;
+  union {
+    deep_sea_hot deep_sea;
+    catch_hot catch_;
+  } fn;
+  union {
+    deep_sea_fam::args deep_sea;
+    catch_fam::args catch_;
+  } fam;
+};
+
+__global__ void __launch_bounds__(BSX_BLOCK) bsx_pair_advance_delta_kernel(const bsx_pair_advance_delta_args a) {
+  __shared__ union {
+    deep_sea_fam::shared deep_sea;
+    catch_fam::shared catch_;
+  } s_fam;
+  __shared__ unsigned int s_cnt[2];
+  if (a.family == BSX_FAM_DEEP_SEA)
+    bsx_advance_delta_body<deep_sea_fam, deep_sea_hot>(a.fam.deep_sea, a.fn.deep_sea, a.paint, a.cells, s_fam.deep_sea, s_cnt);
+  else
+    bsx_advance_delta_body<catch_fam, catch_hot>(a.fam.catch_, a.fn.catch_, a.paint, a.cells, s_fam.catch_, s_cnt);
+}
+
+void bsx_launch_pair_advance_delta(int32_t family, const void* args, const void* fn, int32_t* paint, uint32_t cells, int64_t blocks,
+                                   hipStream_t st) {
+  bsx_pair_advance_delta_args a;
+  a.family = family; a.cells = cells; a.paint = paint;
+  if (family == BSX_FAM_DEEP_SEA) {
+    a.fn.deep_sea = *static_cast<const deep_sea_hot*>(fn);
+    a.fam.deep_sea = *static_cast<const deep_sea_fam::args*>(args);
+  } else {
+    a.fn.catch_ = *static_cast<const catch_hot*>(fn);
+    a.fam.catch_ = *static_cast<const catch_fam::args*>(args);
+  }
+  bsx_pair_advance_delta_kernel<<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, st>>>(a);
+}
+
 extern "C" const char* bsx_strerror(int code) {
   switch (code) {
     case 0: return "ok";

@@ -7,6 +7,7 @@
 #include "bsx_mlp_returns.h"
 #include "bsx_trajectory.h"
 #include "bsx_gumbel_device.h"
+#include "bsx_drawn_returns.h"
 #include "mountain_car_env.h"
 
 static int mountain_car_make(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, mountain_car_env::args* a) {
@@ -104,6 +105,34 @@ extern "C" int bsx_mountain_car_mlp_sample(const bsx_mountain_car_t* cfg, const 
                                             double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
                                             int32_t* actions_out, double* info) {
   return mountain_car_sample(cfg, call, mlp, inv_temperature, state, steps, out, actions_out, info);
+}
+
+// evaluate_sampled_linear / evaluate_sampled_mlp: the sampled closed loop, writing only what the evaluation writes.
+template <class Policy>
+static int mountain_car_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const Policy* policy,
+                                        double inv_temperature, float* state, int32_t* steps, const bsx_linear_eval_t& out,
+                                        double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = (cfg->max_steps < 1 || cfg->max_steps >= (1 << 30)) ? BSX_ERANGE : 0;
+  if (rc == 0) rc = bsx_check_drawn_returns_call(call, policy, inv_temperature, state, steps, out, info, cfg);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_drawn_returns_args e;
+  mountain_car_env::args* a = &e.fam.mountain_car;
+  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
+  a->info = info; a->obs_numel = 3; a->max_steps = cfg->max_steps;
+  return bsx_drawn_returns_call(e, BSX_FAM_MOUNTAIN_CAR, call, policy, inv_temperature, out);
+}
+
+extern "C" int bsx_mountain_car_linear_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call,
+                                                        const bsx_linear_t* linear, double inv_temperature, float* state,
+                                                        int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return mountain_car_sample_evaluate(cfg, call, linear, inv_temperature, state, steps, out, info);
+}
+
+extern "C" int bsx_mountain_car_mlp_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                                     double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                                     double* info) {
+  return mountain_car_sample_evaluate(cfg, call, mlp, inv_temperature, state, steps, out, info);
 }
 
 extern "C" int bsx_group_set_mountain_car(bsx_group_t* g, int32_t index, const bsx_mountain_car_t* cfg, const bsx_call_t* call,

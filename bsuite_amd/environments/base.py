@@ -1343,6 +1343,70 @@ class Environment(dm_env.EnvironmentBase):
     self._launch_steps(getattr(_native.lib, self._mlp_sample_abi), args, T, what)
     return timestep, actions
 
+  _linear_sample_eval_abi = None   # subclass: the C-ABI entry points of evaluate_sampled_linear / evaluate_sampled_mlp
+  _mlp_sample_eval_abi = None      # (cartpole, swing-up, mountain_car)
+
+  def evaluate_sampled_linear(self, weights, observation, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`sample_linear` with the same arguments, returns only: the lanes take the same `num_steps` steps with the same draws in
+    ONE launch (Cartpole, CartpoleSwingup and MountainCar, batched view, counter-based draws, no wrapper).  The call equals,
+    bit for bit in everything it leaves behind and returns,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(linear_logits(weights[row], obs), words(sample_seed, lane, call index), temperature)
+                           ts = step(a); obs = ts.observation
+
+    State, bsuite_info(), episode_counters() and the call index are left bit for bit where sample_linear leaves them, but no
+    TimeStep is written.  Returns the cached `LinearEvaluation` of evaluate_linear — episodes int32 [B], return_sum and
+    episode_return_sum float64 [B], observation float32 [B, *obs_shape] — with the same definitions: the sums as
+    evaluate_policy() defines them, from the float64 reward of each step in step order, and `.observation` the row of step
+    T-1, written once after the loop.  The buffers are shared with evaluate_linear(), evaluate_mlp() and
+    evaluate_sampled_mlp() and overwritten by the next call of any of the four; passing `.observation` back in is legal.
+    weights, observation, policy_index, temperature and sample_seed are sample_linear's: the same shapes and population
+    form, words 0..2 of stream 3 of (sample_seed, global lane id, call index), nothing drawn on a step that resets, no
+    epsilon and no greedy limit (evaluate_linear).  The refusals are sample_linear's, all before any GPU use, without the
+    4 GiB slab (no slab is written).  Calls interleave freely with step / rollout / sample_* / rollout_* / evaluate_* /
+    mark_reset / reset."""
+    what = 'evaluate_sampled_linear'
+    P = self._check_evaluate_linear(weights, observation, num_steps, policy_index, 0.0, 0, what=what, abi='_linear_sample_eval_abi')
+    beta = self._check_sample(what, temperature, sample_seed)
+    self._ensure_allocated()
+    ev, out = self._fused_eval_out()
+    lin = _native.Linear(weights.data_ptr(), P, policy_index.data_ptr() if policy_index is not None else None, 0.0,
+                         int(sample_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(lin), beta) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._linear_sample_eval_abi), args, int(num_steps), what)
+    return ev
+
+  def evaluate_sampled_mlp(self, w1, w2, observation, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`evaluate_sampled_linear` for an agent with one ReLU hidden layer — `sample_mlp` with the same arguments, returns only:
+    the same ONE launch, the same steps and draws, the same `LinearEvaluation`, contract and refusals.  The call equals, bit
+    for bit in everything it leaves behind and returns,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(mlp_logits(w1[row], w2[row], obs), words(sample_seed, lane, call index), temperature)
+                           ts = step(a); obs = ts.observation
+
+    w1: float32 device tensor [H, D+1] or [P, H, D+1]; w2: [3, H+1] or [P, 3, H+1], 1 <= H <= 64; `policy_index` and
+    `observation` as in sample_mlp; temperature and sample_seed as in sample_linear.  A shared pair is kept on chip; a
+    population is read from device memory by every lane on every step: group the lanes by policy.  State, bsuite_info(),
+    episode_counters() and the call index are left where sample_mlp leaves them; no TimeStep is written.  The result buffers
+    are the ones evaluate_linear() uses, overwritten by the next call of evaluate_linear / evaluate_mlp /
+    evaluate_sampled_linear / evaluate_sampled_mlp."""
+    what = 'evaluate_sampled_mlp'
+    P, H = self._check_evaluate_mlp(w1, w2, observation, num_steps, policy_index, 0.0, 0, what=what, abi='_mlp_sample_eval_abi')
+    beta = self._check_sample(what, temperature, sample_seed)
+    self._ensure_allocated()
+    ev, out = self._fused_eval_out()
+    mlp = _native.Mlp(w1.data_ptr(), w2.data_ptr(), H, P, policy_index.data_ptr() if policy_index is not None else None,
+                      0.0, int(sample_seed), observation.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp), beta) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp_sample_eval_abi), args, int(num_steps), what)
+    return ev
+
   def _step(self, action):
     raise NotImplementedError('The batched engine fuses _step/_reset into one kernel; call step().')
 

@@ -76,6 +76,8 @@ class _CartpoleBase(base.Environment):
   _mlp_rollout_abi = 'bsx_cartpole_mlp_rollout'
   _linear_sample_abi = 'bsx_cartpole_linear_sample'
   _mlp_sample_abi = 'bsx_cartpole_mlp_sample'
+  _linear_sample_eval_abi = 'bsx_cartpole_linear_sample_evaluate'
+  _mlp_sample_eval_abi = 'bsx_cartpole_mlp_sample_evaluate'
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

@@ -34,6 +34,8 @@ class MountainCar(base.Environment):
   _mlp_rollout_abi = 'bsx_mountain_car_mlp_rollout'
   _linear_sample_abi = 'bsx_mountain_car_linear_sample'
   _mlp_sample_abi = 'bsx_mountain_car_mlp_sample'
+  _linear_sample_eval_abi = 'bsx_mountain_car_linear_sample_evaluate'
+  _mlp_sample_eval_abi = 'bsx_mountain_car_mlp_sample_evaluate'
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

@@ -127,6 +127,21 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'evaluate_sampled_policy() is not available through {type(self).__name__}: the fused sampled policy '
                      'evaluation has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
 
+  def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused, like evaluate_linear: the sampled evaluation sums the raw environment's rewards
+    (base.Environment.evaluate_sampled_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError(f'evaluate_sampled_linear() is not available through {type(self).__name__}: the fused sampled evaluation '
+                     'has no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def evaluate_sampled_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused, like evaluate_mlp: the sampled evaluation sums the raw environment's rewards
+    (base.Environment.evaluate_sampled_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError(f'evaluate_sampled_mlp() is not available through {type(self).__name__}: the fused sampled hidden-layer '
+                     'evaluation has no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / '
+                     'MountainCar')
+
   def observation_spec(self):
     return self._env.observation_spec()
 
@@ -597,6 +612,22 @@ class ImageObservation(dm_env.EnvironmentBase):
     del logits, num_steps, kwargs
     raise ValueError('evaluate_sampled_policy() is not available through ImageObservation: the fused sampled policy evaluation '
                      'looks its logits up by index observations; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
+    """Refused: the sampled linear evaluation draws its actions from the raw environment's float rows, never images
+    (base.Environment.evaluate_sampled_linear)."""
+    del weights, observation, num_steps, kwargs
+    raise ValueError('evaluate_sampled_linear() is not available through ImageObservation: the fused sampled evaluation draws '
+                     'its actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / '
+                     'CartpoleSwingup / MountainCar')
+
+  def evaluate_sampled_mlp(self, w1, w2, observation, num_steps, **kwargs):
+    """Refused: the sampled hidden-layer evaluation draws its actions from the raw environment's float rows, never images
+    (base.Environment.evaluate_sampled_mlp)."""
+    del w1, w2, observation, num_steps, kwargs
+    raise ValueError('evaluate_sampled_mlp() is not available through ImageObservation: the fused sampled hidden-layer '
+                     'evaluation draws its actions from, and returns, the raw observation rows; call it on an un-wrapped '
+                     'Cartpole / CartpoleSwingup / MountainCar')
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

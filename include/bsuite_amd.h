@@ -591,6 +591,32 @@ int bsx_mountain_car_mlp_sample(const bsx_mountain_car_t* cfg, const bsx_call_t*
                                 double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
                                 int32_t* actions_out, double* info);
 
+/* ---- fused sampled evaluation: the sampled calls above, returns only (cartpole, swing-up, mountain_car; v12, additive) ----
+ * bsx_<family>_linear_sample / bsx_<family>_mlp_sample with the same policy struct, inv_temperature, logits, draws and reset
+ * rule, in ONE launch — the lanes take the same n_steps steps with the same actions — but instead of [n_steps, n_lanes]
+ * slabs the call writes what bsx_<family>_linear_evaluate writes: the three columns of bsx_policy_eval_t — same
+ * definitions, same step order, from the f64 reward of the step — and observation_out [n_lanes, D], the row of step
+ * n_steps - 1, written once after the last step (a thread reads its row of observation_in before it writes its row of
+ * observation_out: the two may be the same buffer).  The policy struct's explore_seed is the SAMPLE SEED, as in the
+ * sampled calls; a lane that resets takes action 0 and draws nothing.  state, steps, info, counters and the call index end
+ * up bit for bit as the sampled call with the same arguments leaves them.
+ * Refusals are those of bsx_<family>_linear_evaluate / bsx_<family>_mlp_evaluate, in their order, with one change: where
+ * the evaluation refuses an epsilon outside [0, 1], these calls return BSX_ERANGE if the struct's epsilon is not 0.0 (NaN
+ * included) or inv_temperature is not a finite number > 0.  No slab is written, so there is no 4 GiB refusal.  n_lanes == 0
+ * returns 0 and launches nothing.  Asynchronous on call->hip_stream, no allocation, no synchronisation, graph-capturable. */
+int bsx_cartpole_linear_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                        double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                        double* info);
+int bsx_mountain_car_linear_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                            double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                            double* info);
+int bsx_cartpole_mlp_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                     double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                     double* info);
+int bsx_mountain_car_mlp_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                         double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                         double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */

@@ -21,7 +21,8 @@
  *               U < epsilon, RandInt(num_actions) — word 2.  Nothing is drawn by a lane that resets on that
  *               call, nor when epsilon == 0; streams 0 and 1 never depend on it.
  *               3 = the Gumbel draws of a softmax policy inside a fused sampled trajectory
- *               (bsx_<family>_linear_sample / bsx_<family>_mlp_sample); its key is the caller's sample seed and a
+ *               (bsx_<family>_linear_sample / bsx_<family>_mlp_sample) and of its returns-only form
+ *               (bsx_<family>_linear_sample_evaluate / bsx_<family>_mlp_sample_evaluate); its key is the caller's sample seed and a
  *               (lane, step) triple uses words 0..2 of block 0, word a for action a (csrc/bsx_gumbel.h).  Nothing is
  *               drawn by a lane that resets on that call; an epsilon-greedy call with the same seed shares no word.
  *               The fused sampled rollouts from a table of logits (bsx_<family>_policy_sample /
