@@ -118,6 +118,13 @@ class PolicyLogits(ctypes.Structure):
               ('sample_seed', ctypes.c_uint64), ('actions_out', ctypes.c_void_p)]
 
 
+class PolicyEmbedding(ctypes.Structure):
+  """bsx_policy_embedding_t: the pair of matrices of bsx_<family>_embedding_rollout / bsx_<family>_embedding_evaluate."""
+  _fields_ = [('w1', ctypes.c_void_p), ('w2', ctypes.c_void_p), ('n_cells', ctypes.c_int32), ('n_hidden', ctypes.c_int32),
+              ('n_actions', ctypes.c_int32), ('n_policies', ctypes.c_int32), ('policy_index', ctypes.c_void_p),
+              ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64), ('actions_out', ctypes.c_void_p)]
+
+
 class PolicyEvalPtrs(ctypes.Structure):
   """bsx_policy_eval_t: the three output columns of bsx_<family>_policy_evaluate."""
   _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p)]
@@ -236,6 +243,15 @@ _SIGS = {
                                              PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_catch_policy_sample_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
                                           PolicyEvalPtrs, _P], ctypes.c_int),
+    # rollout_embedding / evaluate_embedding: the signatures of *_policy_rollout / *_policy_evaluate with a pair of matrices
+    'bsx_deep_sea_embedding_rollout': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
+                                        TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_catch_embedding_rollout': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
+                                     TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_deep_sea_embedding_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
+                                         PolicyEvalPtrs, _P], ctypes.c_int),
+    'bsx_catch_embedding_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
+                                      PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_bandit_step': ([ctypes.POINTER(BanditCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                         ctypes.c_int),
     'bsx_memory_chain_step': ([ctypes.POINTER(MemoryChainCfg), ctypes.POINTER(Call), _P, _P, _P,

@@ -59,4 +59,7 @@ struct bandit_env : small_regs_defaults {
   }
 };
 
+template <>
+struct small_obs_duo_group<bandit_env> { static constexpr bool value = true; };   // (small_obs.h)
+
 #endif  // BSX_BANDIT_ENV_H_

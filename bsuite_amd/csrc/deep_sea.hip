@@ -15,6 +15,7 @@
 // Decoupling the two is what makes the store stream fast: single-kernel variants that advance
 // lanes, synchronise and then store (per-block 230 KB tiles, or flat 16 KiB runs with ping-pong
 // state) measured 5.1-5.5 TB/s against 6.2-6.4 TB/s for this pair (profiles/r01/ab_*.log).
+#include "bsx_embed_device.h"
 #include "bsx_pair_host.h"
 #include "bsx_tab_eval.h"
 #include "bsx_tab_sample_device.h"
@@ -249,6 +250,31 @@ extern "C" int bsx_deep_sea_policy_sample_evaluate(const bsx_deep_sea_t* cfg, co
   bsx_tab_softmax_args s;
   deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);     // (no action column, no TimeStep)
   return bsx_tab_softmax_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
+}
+
+extern "C" int bsx_deep_sea_embedding_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                        int32_t* state, bsx_timestep_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_embed_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_embed_args s;
+  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_deep_sea_policy_rollout)
+  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &s.fam.deep_sea);
+  if (rc != 0) return rc;
+  s.fam.deep_sea.action = nullptr;
+  return bsx_embed_call(s, BSX_FAM_DEEP_SEA, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+}
+
+extern "C" int bsx_deep_sea_embedding_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                         int32_t* state, bsx_policy_eval_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_embed_eval_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_embed_args s;
+  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);          // (no action column, no TimeStep)
+  return bsx_embed_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
 }
 
 extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_deep_sea_t* cfg,

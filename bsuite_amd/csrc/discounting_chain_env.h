@@ -85,4 +85,7 @@ struct discounting_chain_env : small_regs_defaults {
   }
 };
 
+template <>
+struct small_obs_duo_group<discounting_chain_env> { static constexpr bool value = true; };   // (small_obs.h)
+
 #endif  // BSX_DISCOUNTING_CHAIN_ENV_H_

@@ -814,13 +814,25 @@ __global__ void __launch_bounds__(BSX_BLOCK) small_obs_group_kernel(const typena
   small_obs_group_body<Env>(table[w.seg], w.block, s_obs, s_cnt);
 }
 
+// bandit and discounting_chain — the two families whose whole step is a register-resident row of one or two floats — share
+// ONE kernel for their single-family groups, off every measured path: small_obs_duo_group_kernel (sweep_mixed.hip), the
+// family a uniform switch and each branch small_obs_group_body<Env> unchanged.  Their env headers say so here.
+template <class Env>
+struct small_obs_duo_group { static constexpr bool value = false; };
+// launch of a single-family group of bandit or discounting_chain (g->family says which; sweep_mixed.hip)
+int bsx_small_duo_launch(bsx_group* g, int phase, hipStream_t st);
+
 template <class Env>
 static int small_obs_group_launch(bsx_group* g, int phase, hipStream_t st) {
-  if (phase == 1) return 0;                 // one kernel per step: everything happens in phase 0
-  const dim3 grid((unsigned)g->total_blocks), block(BSX_BLOCK);
-  const typename Env::args* table = (const typename Env::args*)g->d_args;
-  small_obs_group_kernel<Env><<<grid, block, g->lds_bytes, st>>>(table, g->index1());
-  return (int)hipGetLastError();
+  if constexpr (small_obs_duo_group<Env>::value) {
+    return bsx_small_duo_launch(g, phase, st);
+  } else {
+    if (phase == 1) return 0;               // one kernel per step: everything happens in phase 0
+    const dim3 grid((unsigned)g->total_blocks), block(BSX_BLOCK);
+    const typename Env::args* table = (const typename Env::args*)g->d_args;
+    small_obs_group_kernel<Env><<<grid, block, g->lds_bytes, st>>>(table, g->index1());
+    return (int)hipGetLastError();
+  }
 }
 
 // A BSX_FAM_SMALL_MIXED group holds segments of ANY of the families in this file: every segment's

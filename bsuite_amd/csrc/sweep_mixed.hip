@@ -47,6 +47,34 @@ int bsx_small_mixed_launch(bsx_group* g, int phase, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------ single-family groups of bandit / discounting_chain
+// (small_obs_duo_group, small_obs.h): ONE kernel for both, off every measured path — only a SweepBatch prepared without the
+// mixed small-family group launches it.  `table` is the device array of that family's args, one per segment; the family is a
+// uniform switch and each branch is small_obs_group_body<Env> on the segment and the block bsx_group_find names.
+struct small_obs_duo_group_args {
+  const void* table;
+  bsx_group_index gi;
+  int32_t family;
+};
+
+__global__ void __launch_bounds__(BSX_BLOCK) small_obs_duo_group_kernel(const small_obs_duo_group_args a) {
+  extern __shared__ __attribute__((aligned(16))) float s_obs[];
+  __shared__ unsigned int s_cnt[2];
+  const bsx_group_slot w = bsx_group_find(a.gi, (int)blockIdx.x);
+  if (a.family == BSX_FAM_BANDIT)
+    small_obs_group_body<bandit_env>(static_cast<const bandit_env::args*>(a.table)[w.seg], w.block, s_obs, s_cnt);
+  else
+    small_obs_group_body<discounting_chain_env>(static_cast<const discounting_chain_env::args*>(a.table)[w.seg], w.block, s_obs, s_cnt);
+}
+
+int bsx_small_duo_launch(bsx_group* g, int phase, hipStream_t st) {
+  if (phase == 1) return 0;                 // one kernel per step: everything happens in phase 0
+  small_obs_duo_group_args a;
+  a.table = g->d_args; a.gi = g->index1(); a.family = g->family;
+  small_obs_duo_group_kernel<<<dim3((unsigned)g->total_blocks), dim3(BSX_BLOCK), g->lds_bytes, st>>>(a);
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------ whole-sweep group, phase 0
 // BSX_FAM_SWEEP_MIXED: ONE launch advances every lane of a heterogeneous sweep — the lane-advance of
 // deep_sea / catch / mnist segments (whose observation stream follows as phase 1, pair_mixed.hip) and the

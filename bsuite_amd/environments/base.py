@@ -1024,6 +1024,101 @@ class Environment(dm_env.EnvironmentBase):
     self._launch_steps(getattr(_native.lib, self._policy_sample_eval_abi), args, int(num_steps), what)
     return ev
 
+  _embedding_rollout_abi = None   # subclass: the C-ABI entry points of rollout_embedding / evaluate_embedding (deep_sea,
+  _embedding_eval_abi = None      # catch)
+
+  def _check_embedding(self, w1, w2, num_steps, policy_index, epsilon, explore_seed, what, abi):
+    """The refusals of rollout_embedding() and evaluate_embedding() (`what`), all before any GPU use, nothing allocated: the
+    environment's part (_check_policy_env), the pair of matrices, the population rule, then epsilon and the seed as
+    _check_rollout_policy refuses them.  Returns (P, H)."""
+    self._check_policy_env(what, num_steps, abi=abi)
+    C, A = int(np.prod(self._board_shape)), int(self._num_actions)
+    ok = lambda w: torch.is_tensor(w) and w.dtype == torch.float32 and w.device == self._device and w.numel() > 0 and w.is_contiguous()
+    H = int(w1.shape[-1]) if ok(w1) and w1.dim() in (2, 3) else 0
+    if (not ok(w1) or not ok(w2) or w1.dim() not in (2, 3) or w2.dim() != w1.dim() or not 1 <= H <= _native.MLP_MAX_HIDDEN
+        or tuple(w1.shape[-2:]) != (C + 2, H) or tuple(w2.shape[-2:]) != (A, H + 1) or w1.shape[:-2] != w2.shape[:-2]):
+      raise ValueError(f'{what}: w1 and w2 must be contiguous float32 tensors of shapes ({C + 2}, H) and ({A}, H + 1), or '
+                       f'(P, {C + 2}, H) and (P, {A}, H + 1), with 1 <= H <= {_native.MLP_MAX_HIDDEN}, on {self._device}')
+    P = 1 if w1.dim() == 2 else int(w1.shape[0])
+    self._check_policy_population(what, P, policy_index)
+    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
+      raise ValueError(f'{what}: epsilon must be a number in [0, 1], got {epsilon!r}')
+    if isinstance(explore_seed, bool) or not isinstance(explore_seed, (int, np.integer)) or not 0 <= int(explore_seed) < (1 << 64):
+      raise ValueError(f'{what}: explore_seed must be an integer in [0, 2^64), got {explore_seed!r}')
+    return P, H
+
+  def _policy_embedding(self, w1, w2, P, H, policy_index, epsilon, explore_seed, actions):
+    return _native.PolicyEmbedding(w1.data_ptr(), w2.data_ptr(), int(np.prod(self._board_shape)), H, int(self._num_actions), P,
+                                   policy_index.data_ptr() if policy_index is not None else None, float(epsilon),
+                                   int(explore_seed), actions.data_ptr() if actions is not None else None)
+
+  def rollout_embedding(self, w1, w2, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`rollout_policy` for an agent whose policy is a small network on the one-hot board (a DQN actor, an ES / CEM population of
+    networks): a closed-loop rollout of `num_steps` steps in ONE launch, the actions the greedy — with `epsilon`, epsilon-greedy
+    — choice of a network with one ReLU hidden layer whose first layer is a row gather on the lane's own index observation
+    (DeepSea and Catch, batched view, observation_mode='index', counter-based draws, no wrapper).
+
+    With C the cells of `board_shape`, K the entries of an index row (deep_sea 1, catch 2), A = action_spec().num_values
+    (deep_sea 2, catch 3) and H hidden units, 1 <= H <= 64: `w1` is a contiguous float32 device tensor [C + 2, H] — row c + 1 the
+    embedding of cell c, row 0 the row a -1 entry selects (utils.observations.index_embedding's layout, so
+    `index_embedding(obs, w1)` stays usable as it is), row C + 1 the hidden bias — and `w2` float32 [A, H + 1], the bias in the
+    last column (evaluate_mlp's `w2`).  A population is [P, C + 2, H] and [P, A, H + 1] with `policy_index`, int32 [B], naming
+    each lane's pair (clamped to [0, P-1]; with one pair it must be None).  Only 4-byte alignment is assumed: a view that
+    starts one float into a buffer is fine.  Returns `(ts, actions)` as rollout_policy does and equals, bit for bit in
+    everything it returns and everything it leaves behind,
+
+        for t in range(T): a = 0 where the lane resets on this call, else select(observation before the call)
+                           ts[t] = step(a); actions[t] = a
+
+    select is utils.observations.embedding_select followed by rollout_policy's epsilon coin — float32, every add and every
+    multiply rounded on its own (csrc/bsx_embed.h):
+
+        l_a = w2[a][H]
+        for j in range(H): s = w1[C+1][j]; for k in range(K): s = s + w1[cell_k + 1][j]
+                           h = s if s > 0 else +0.0;  l_a = l_a + w2[a][j] * h
+        best = 0; for a in 1..A-1: if l_a > l_best: best = a          the lowest index wins a tie, a NaN never wins
+
+    cell_k is entry k of the index row in order (catch: ball, then paddle; the same cell twice is added twice), clamped to
+    [-1, C-1].  With epsilon > 0 a lane that does not reset draws U() and, if U < epsilon, takes RandInt(A) instead: stream 2 of
+    (explore_seed, global lane id, call index), word for word rollout_policy's rule; nothing is computed or drawn on a step
+    that resets, and the environment's own stream 0 is untouched, so `rollout(actions)` on a twin reproduces `ts`.  A shared
+    pair whose on-chip copy fits 15 KiB (catch/0 up to H = 64, deep_sea N = 10 up to H = 32) is kept on chip; a larger one and
+    every population is read from device memory.  State, bsuite_info(), episode_counters(), invalid_action_count() and the call
+    index are left as T step() calls leave them; calls interleave freely with step / rollout / rollout_policy /
+    evaluate_policy / sample_policy / mark_reset / reset.  Output buffers are cached per T, shared with rollout_policy(), and
+    overwritten by the next call of the same T."""
+    what = 'rollout_embedding'
+    P, H = self._check_embedding(w1, w2, num_steps, policy_index, epsilon, explore_seed, what, '_embedding_rollout_abi')
+    self._ensure_allocated()
+    T = int(num_steps)
+    if T not in self._policy_rollout_out:
+      actions = torch.empty((T, self._batch), dtype=torch.int32, device=self._device)
+      self._policy_rollout_out[T] = self._new_outputs((T, self._batch), dict(device=self._device)) + (actions,)
+    _, ptrs, timestep, actions = self._policy_rollout_out[T]
+    pol = self._policy_embedding(w1, w2, P, H, policy_index, epsilon, explore_seed, actions)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), ptrs,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._embedding_rollout_abi), args, T, what)
+    return timestep, actions
+
+  def evaluate_embedding(self, w1, w2, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`rollout_embedding` with the same arguments, returns only: the lanes take the same `num_steps` steps with the same draws
+    in ONE launch, and state, bsuite_info(), episode_counters(), invalid_action_count() and the call index are left bit for bit
+    where rollout_embedding leaves them, but no TimeStep is written.  Returns the cached `PolicyEvaluation` of evaluate_policy
+    — episodes int32, return_sum and episode_return_sum float64, [B] each — with the same definitions: the float64 reward of
+    the step before its rounding to float32, summed in step order (evaluate_policy has the loop).  The refusals are
+    rollout_embedding's.  The three buffers are shared with evaluate_policy() and overwritten by the next call of either."""
+    what = 'evaluate_embedding'
+    P, H = self._check_embedding(w1, w2, num_steps, policy_index, epsilon, explore_seed, what, '_embedding_eval_abi')
+    self._ensure_allocated()
+    ev = self._policy_evaluation_out()
+    pol = self._policy_embedding(w1, w2, P, H, policy_index, epsilon, explore_seed, None)
+    out = _native.PolicyEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), out,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._embedding_eval_abi), args, int(num_steps), what)
+    return ev
+
   _linear_eval_abi = None   # subclass: the C-ABI entry point of evaluate_linear (cartpole, swing-up, mountain_car)
 
   def _check_fused_eval(self, what, abi, num_steps, epsilon, explore_seed):

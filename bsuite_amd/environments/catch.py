@@ -49,6 +49,8 @@ class Catch(base.Environment):
   _policy_eval_abi = 'bsx_catch_policy_evaluate'
   _policy_sample_abi = 'bsx_catch_policy_sample'
   _policy_sample_eval_abi = 'bsx_catch_policy_sample_evaluate'
+  _embedding_rollout_abi = 'bsx_catch_embedding_rollout'
+  _embedding_eval_abi = 'bsx_catch_embedding_evaluate'
 
   @property
   def policy_num_states(self) -> int:

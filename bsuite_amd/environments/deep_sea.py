@@ -83,6 +83,8 @@ class DeepSea(base.Environment):
   _policy_eval_abi = 'bsx_deep_sea_policy_evaluate'
   _policy_sample_abi = 'bsx_deep_sea_policy_sample'
   _policy_sample_eval_abi = 'bsx_deep_sea_policy_sample_evaluate'
+  _embedding_rollout_abi = 'bsx_deep_sea_embedding_rollout'
+  _embedding_eval_abi = 'bsx_deep_sea_embedding_evaluate'
 
   @property
   def policy_num_states(self) -> int:

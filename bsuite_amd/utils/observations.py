@@ -1,4 +1,5 @@
-"""Helpers for index observations (observation_mode='index' of deep_sea and catch) and for linear and hidden-layer policies on
+"""Helpers for index observations (observation_mode='index' of deep_sea and catch: dense boards, table keys, and hidden-layer
+policies on the index row, `env.rollout_embedding`, `env.evaluate_embedding`) and for linear and hidden-layer policies on
 the float observations of the physics families (`env.evaluate_linear`, `env.evaluate_mlp`, `env.sample_linear`, `env.sample_mlp`).
 
 An index observation names the hot cells of a one-hot board: int32 `[..., K]`, each entry a flat cell number of the
@@ -60,6 +61,52 @@ def index_embedding(index: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
   rows of ball and paddle are summed, also when they name the same cell — there the dense board holds ONE 1, so the
   two forms differ on the step where the paddle catches the ball; use index_to_dense where that matters."""
   return table[index.to(torch.int64) + 1].sum(dim=-2)
+
+
+def embedding_logits(w1: torch.Tensor, w2: torch.Tensor, index_rows: torch.Tensor, return_preactivations: bool = False):
+  """The logits `[B, A]` (float32) of a policy with one ReLU hidden layer on index observations `[B, K]`, exactly as
+  `env.rollout_embedding` / `env.evaluate_embedding` compute them inside their kernel (csrc/bsx_embed.h).  `w1` is float32
+  `[C + 2, H]` — row c + 1 the embedding of cell c, row 0 the row a -1 entry selects (`index_embedding`'s layout), row C + 1
+  the hidden bias — and `w2` `[A, H + 1]`, the bias in the last column (one pair), or `[B, C + 2, H]` and `[B, A, H + 1]` (lane
+  b's own pair, e.g. `population[policy_index.clamp(0, P - 1).long()]`).
+
+    l_a = w2[a][H]
+    for j = 0..H-1: s = w1[C+1][j]; for k = 0..K-1: s = s + w1[cell_k + 1][j]    float32, every multiply and every add rounded
+                    h = s if s > 0 else +0.0                                      on its own: separate torch ops, never addcmul
+                    l_a = l_a + w2[a][j] * h                                      or matmul; a NaN s gives h = 0
+
+  cell_k is entry k of the row in order (catch: ball, then paddle; the same cell twice is added twice, as index_embedding
+  does), clamped to [-1, C - 1].  With `return_preactivations` the result is `(logits, s)`, `s` float32 `[B, H]`."""
+  B, K = int(index_rows.shape[0]), int(index_rows.shape[1])
+  a1 = w1 if w1.dim() == 3 else w1.unsqueeze(0).expand(B, -1, -1)
+  a2 = w2 if w2.dim() == 3 else w2.unsqueeze(0).expand(B, -1, -1)
+  C, H = int(a1.shape[1]) - 2, int(a1.shape[2])
+  rows = index_rows.to(torch.int64).clamp(-1, C - 1) + 1                                    # [B, K]
+  s = a1[:, C + 1, :].clone()                                                               # [B, H]: all hidden units at once
+  for k in range(K):
+    e = torch.gather(a1, 1, rows[:, k].reshape(B, 1, 1).expand(B, 1, H))[:, 0, :]
+    s = s + e
+  h = torch.where(s > 0, s, torch.zeros_like(s))
+  logits = a2[:, :, H].clone()
+  for j in range(H):
+    prod = a2[:, :, j] * h[:, j:j + 1]
+    logits = logits + prod
+  return (logits, s) if return_preactivations else logits
+
+
+def embedding_select(w1: torch.Tensor, w2: torch.Tensor, index_rows: torch.Tensor) -> torch.Tensor:
+  """The greedy action `[B]` (int32) of `embedding_logits(w1, w2, index_rows)`, exactly as `env.rollout_embedding` selects it
+  inside its kernel (csrc/bsx_embed.h):
+
+    best = 0; for a = 1..A-1: if l_a > l_best: best = a                the lowest index wins a tie, a NaN never wins"""
+  logits = embedding_logits(w1, w2, index_rows)
+  best = torch.zeros(logits.shape[0], dtype=torch.int32, device=logits.device)
+  l_best = logits[:, 0]
+  for a in range(1, int(logits.shape[1])):
+    better = logits[:, a] > l_best
+    best = torch.where(better, torch.full_like(best, a), best)
+    l_best = torch.where(better, logits[:, a], l_best)
+  return best
 
 
 def linear_select(weights: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:

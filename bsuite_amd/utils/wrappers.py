@@ -127,6 +127,19 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'evaluate_sampled_policy() is not available through {type(self).__name__}: the fused sampled policy '
                      'evaluation has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
 
+  def rollout_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like rollout_policy: the fused rollout records the raw environment's rewards (base.Environment.rollout_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError(f'rollout_embedding() is not available through {type(self).__name__}: the fused hidden-layer rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like evaluate_policy: the fused evaluation sums the raw environment's rewards
+    (base.Environment.evaluate_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError(f'evaluate_embedding() is not available through {type(self).__name__}: the fused hidden-layer evaluation '
+                     'has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
   def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
     """Refused, like evaluate_linear: the sampled evaluation sums the raw environment's rewards
     (base.Environment.evaluate_sampled_linear)."""
@@ -612,6 +625,20 @@ class ImageObservation(dm_env.EnvironmentBase):
     del logits, num_steps, kwargs
     raise ValueError('evaluate_sampled_policy() is not available through ImageObservation: the fused sampled policy evaluation '
                      'looks its logits up by index observations; call it on an un-wrapped DeepSea / Catch')
+
+  def rollout_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like rollout_policy: a fused hidden-layer rollout returns index observations, never images
+    (base.Environment.rollout_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError('rollout_embedding() is not available through ImageObservation: the fused hidden-layer rollout returns index '
+                     'observations; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like evaluate_policy: the fused hidden-layer evaluation gathers its first layer by index observations
+    (base.Environment.evaluate_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError('evaluate_embedding() is not available through ImageObservation: the fused hidden-layer evaluation gathers '
+                     'its first layer by index observations; call it on an un-wrapped DeepSea / Catch')
 
   def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
     """Refused: the sampled linear evaluation draws its actions from the raw environment's float rows, never images

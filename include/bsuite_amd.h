@@ -384,6 +384,53 @@ int bsx_deep_sea_policy_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_cal
 int bsx_catch_policy_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
                                      int32_t* state, bsx_policy_eval_t out, double* info);
 
+/* ---- fused closed loops from a hidden-layer policy on the index row (deep_sea, catch; v12, additive) ----
+ * bsx_<family>_policy_rollout / bsx_<family>_policy_evaluate with another action source, in ONE launch: instead of a table
+ * entry, the greedy action of a network with one ReLU hidden layer whose first layer is a row gather on the lane's index
+ * observation BEFORE the call — w1 float32 [n_policies, n_cells + 2, n_hidden] (row c + 1 the embedding of cell c, row 0 the
+ * row a -1 entry selects, row n_cells + 1 the hidden bias) and w2 float32 [n_policies, n_actions, n_hidden + 1] (the bias in
+ * the last column); n_cells = the cells of the board (deep_sea N * N, catch rows * columns), n_actions: deep_sea 2, catch 3.
+ * Per step t and lane i, float32 with every add and every multiply rounded on its own (csrc/bsx_embed.h):
+ *     a = 0                                   if the lane resets on this call
+ *       = RandInt(n_actions)                  else if epsilon > 0 and U() < epsilon
+ *       = best                                else:
+ *         l_a = w2[a][H]
+ *         for j = 0 .. H-1:  s = w1[C+1][j];  for k = 0 .. K-1: s = s + w1[cell_k + 1][j];  h = s > 0 ? s : +0.0
+ *                            l_a = l_a + w2[a][j] * h
+ *         best = 0; for a = 1 .. A-1: if l_a > l_best: best = a
+ *     then exactly step(a).
+ * cell_k: entry k of the lane's index row in order (catch: ball, then paddle; the same cell twice is added twice), clamped
+ * to [-1, n_cells - 1]; the row of a population is policy_index[i] clamped to [0, n_policies - 1]; U() and RandInt are those
+ * of bsx_<family>_policy_rollout (stream BSX_STREAM_POLICY of (explore_seed, global lane id, the step's call index)); a lane
+ * that resets computes and draws nothing; the environment's own stream is untouched.
+ *   bsx_<family>_embedding_rollout    writes what bsx_<family>_policy_rollout writes: `out` [n_steps, n_lanes(, K)] and
+ *                                     actions_out[t * n_lanes + i] = a
+ *   bsx_<family>_embedding_evaluate   takes the same steps with the same draws and writes what bsx_<family>_policy_evaluate
+ *                                     writes: the three columns of bsx_policy_eval_t; actions_out is not looked at
+ * State, info, counters and the call index end up as n_steps step() calls leave them, the same after either call.
+ * Refusals (all before any device work), in the order of bsx_<family>_policy_rollout / _policy_evaluate: BSX_EMODE as there;
+ * BSX_EINVAL also for n_cells or n_actions other than the family's and for n_hidden outside [1, 64]; BSX_ERANGE for an
+ * epsilon outside [0, 1]; BSX_ENULL as there (w1 and w2 in the table's place); and last BSX_EALIGN for w1 or w2 that is not
+ * 4-byte aligned — no wider alignment is assumed.  n_lanes == 0 returns 0 and launches nothing.  Asynchronous on
+ * call->hip_stream, no allocation, no synchronisation, graph-capturable. */
+typedef struct {
+  const float*   w1;             /* device [n_policies, n_cells + 2, n_hidden]                     */
+  const float*   w2;             /* device [n_policies, n_actions, n_hidden + 1]                   */
+  int32_t        n_cells, n_hidden, n_actions, n_policies;
+  const int32_t* policy_index;   /* device [n_lanes] or NULL when n_policies == 1                  */
+  double         epsilon;
+  uint64_t       explore_seed;
+  int32_t*       actions_out;    /* device [n_steps, n_lanes] (bsx_<family>_embedding_rollout)     */
+} bsx_policy_embedding_t;
+int bsx_deep_sea_embedding_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                   int32_t* state, bsx_timestep_t out, double* info);
+int bsx_catch_embedding_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                int32_t* state, bsx_timestep_t out, double* info);
+int bsx_deep_sea_embedding_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                    int32_t* state, bsx_policy_eval_t out, double* info);
+int bsx_catch_embedding_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                 int32_t* state, bsx_policy_eval_t out, double* info);
+
 /* ---- bandit : bsuite/environments/bandit.py:35-73 ----------------------------------------- */
 #define BSX_BANDIT_MAX_ACTIONS 32
 typedef struct {
