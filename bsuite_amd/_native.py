@@ -125,6 +125,13 @@ class PolicyEmbedding(ctypes.Structure):
               ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64), ('actions_out', ctypes.c_void_p)]
 
 
+class PolicyEmbeddingSample(ctypes.Structure):
+  """bsx_policy_embedding_sample_t: the pair of matrices of bsx_<family>_embedding_sample / bsx_<family>_embedding_sample_evaluate."""
+  _fields_ = [('w1', ctypes.c_void_p), ('w2', ctypes.c_void_p), ('n_cells', ctypes.c_int32), ('n_hidden', ctypes.c_int32),
+              ('n_actions', ctypes.c_int32), ('n_policies', ctypes.c_int32), ('policy_index', ctypes.c_void_p),
+              ('inv_temperature', ctypes.c_double), ('sample_seed', ctypes.c_uint64), ('actions_out', ctypes.c_void_p)]
+
+
 class PolicyEvalPtrs(ctypes.Structure):
   """bsx_policy_eval_t: the three output columns of bsx_<family>_policy_evaluate."""
   _fields_ = [('episodes', ctypes.c_void_p), ('return_sum', ctypes.c_void_p), ('episode_return_sum', ctypes.c_void_p)]
@@ -252,6 +259,15 @@ _SIGS = {
                                          PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_catch_embedding_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
                                       PolicyEvalPtrs, _P], ctypes.c_int),
+    # sample_embedding / evaluate_sampled_embedding: the same signatures with the sampled pair of matrices
+    'bsx_deep_sea_embedding_sample': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample), _P,
+                                       TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_catch_embedding_sample': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample), _P,
+                                    TimeStepPtrs, _P], ctypes.c_int),
+    'bsx_deep_sea_embedding_sample_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample),
+                                                _P, PolicyEvalPtrs, _P], ctypes.c_int),
+    'bsx_catch_embedding_sample_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample), _P,
+                                             PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_bandit_step': ([ctypes.POINTER(BanditCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                         ctypes.c_int),
     'bsx_memory_chain_step': ([ctypes.POINTER(MemoryChainCfg), ctypes.POINTER(Call), _P, _P, _P,

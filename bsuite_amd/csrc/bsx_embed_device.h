@@ -3,12 +3,14 @@
 // (bsx_embed_kernel, embed.hip), the two bodies of its step loop, its launcher and the checks the four entry points share.
 // The closed loops of bsx_policy_rollout_kernel and bsx_tab_eval_body (bsx_pair_device.h) with another action SOURCE: instead
 // of a uint8 table entry the lane takes the greedy action of a one-hidden-layer network on its index row (bsx_embed.h); the
-// epsilon coin behind it is bsx_policy_select's, unchanged.
+// epsilon coin behind it is bsx_policy_select's, unchanged.  bsx_<family>_embedding_sample / _embedding_sample_evaluate
+// (sample_embedding, evaluate_sampled_embedding) are the same kernel with a third uniform switch: the lane takes a draw from
+// softmax(logits / temperature) of the same network by Gumbel-max (bsx_embed_sample.h) — no epsilon there.
 #ifndef BSX_EMBED_DEVICE_H_
 #define BSX_EMBED_DEVICE_H_
 
 #include "bsx_pair_host.h"
-#include "bsx_embed.h"
+#include "bsx_embed_sample.h"         // bsx_embed.h, bsx_tab_sample.h (bsx_gumbel_draws, bsx_gumbel_select_n)
 #include "catch_fam.h"
 #include "deep_sea_fam.h"
 
@@ -18,19 +20,22 @@ struct bsx_embed_net_args {
   const float* w2;               // [n_policies, A, n_hidden + 1]; 4-byte aligned, no more
   const int32_t* policy_index;   // [n_lanes], nullptr when n_policies == 1
   int32_t* actions_out;          // [n_steps, n_lanes] (the recording call's alone)
-  double epsilon;
-  uint64_t explore_seed;
+  double epsilon;                // (greedy)
+  uint64_t explore_seed;         // (greedy)
+  double beta;                   // (drawn) 1 / temperature: finite, > 0 (the entry points check)
+  uint64_t sample_seed;          // (drawn)
   int32_t n_cells, n_hidden, n_policies;
   int32_t in_lds;                // one shared pair whose copy fits BSX_EMBED_LDS_BYTES: every workgroup stages it in LDS
 };
 
 // The family and the kind of call are uniform switches per launch, so the arguments are a tagged struct: `family` says which
-// member of `fam` is set, `record` which of `rows` (with fam's TimeStep pointers and p.actions_out) and `out` is written.
+// member of `fam` is set, `record` which of `rows` (with fam's TimeStep pointers and p.actions_out) and `out` is written,
+// `drawn` which of p's (epsilon, explore_seed) and (beta, sample_seed) is read.
 struct bsx_embed_args {
   int32_t family;                // BSX_FAM_DEEP_SEA or BSX_FAM_CATCH
   int32_t n_steps;
   int32_t record;                // 1: rollout_embedding (TimeStep, index rows, actions); 0: evaluate_embedding (returns only)
-  int32_t _pad;
+  int32_t drawn;                 // 1: sample_embedding / evaluate_sampled_embedding (Gumbel-max); 0: greedy with an epsilon coin
   bsx_embed_net_args p;
   int32_t* rows;                 // [n_steps, n_lanes, K] index observations (record)
   bsx_policy_eval_t out;         // (returns only)
@@ -68,20 +73,32 @@ struct bsx_embed_catch {
   __device__ static __forceinline__ const fam::args& of(const bsx_embed_args& k) { return k.fam.catch_; }
   __device__ static __forceinline__ hot fn(const fam::args& a) { return hot{a.rows, a.columns}; }
 };
+// The action source of a body: the greedy action behind an epsilon coin, or — bsx_embed_drawn<family> — a draw from the softmax.
+struct bsx_embed_greedy {};
+struct bsx_embed_gumbel {};
+template <class F>
+struct bsx_embed_drawn : F {};
+template <class F>
+struct bsx_embed_source_of { typedef bsx_embed_greedy type; };
+template <class F>
+struct bsx_embed_source_of<bsx_embed_drawn<F>> { typedef bsx_embed_gumbel type; };
 
 // The pair staged in LDS, typed as such and read in 16-byte chunks: through a generic pointer the look-up would be a FLAT
 // load (bsx_policy_rollout_kernel has what that costs).
 typedef const bsx_f4 __attribute__((address_space(3)))* bsx_embed_lds4;
 
 // The greedy action of a lane that does not reset: cells -> rows of w1 -> the hidden units, consumed as they are produced ->
-// argmax.  The two look-ups are two branches, kept apart by the empty asm, and never one load through a generic pointer:
+// argmax — or, for Source = bsx_embed_gumbel, the lane's draw: the same logits -> block 0 of stream BSX_STREAM_SAMPLE ->
+// bsx_gumbel_select_n (the float64 scores come after the hidden-unit loop, when only the A logits are live).  The two
+// look-ups are two branches, kept apart by the empty asm, and never one load through a generic pointer:
 //   LDS     16-byte typed loads from the staged copy (bsx_embed.h has its layout): per four hidden units one chunk of each of
 //           the lane's K rows, one of the bias row (the same address in every lane: a broadcast) and four of the transposed
 //           w2 (broadcasts too).  The floats of a chunk beyond H are padding that is never looked at.
 //   global  typed 4-byte loads from the lane's own pair (`prow`: its row of a population, 0 for a shared pair) — no wider
 //           alignment than a float's is assumed.
-template <int K, int A, class HotFn>
-__device__ __forceinline__ int bsx_embed_best(const HotFn& fn, int32_t st, const bsx_embed_net_args& p, const float* s_net, int prow) {
+template <int K, int A, class Source = bsx_embed_greedy, class HotFn>
+__device__ __forceinline__ int bsx_embed_best(const HotFn& fn, int32_t st, const bsx_embed_net_args& p, const float* s_net, int prow,
+                                              uint64_t lane = 0, uint64_t step = 0) {
   static_assert(K >= 1 && K <= BSX_EMBED_MAX_K && A >= 2 && A <= BSX_EMBED_MAX_ACTIONS, "deep_sea or catch");
   const int C = p.n_cells, H = p.n_hidden;
   int cell[2];
@@ -143,14 +160,18 @@ __device__ __forceinline__ int bsx_embed_best(const HotFn& fn, int32_t st, const
       bsx_embed_accumulate(l, w2j, bsx_mlp_relu(bsx_embed_preactivation(gb[j], ek, K)), A);
     }
   }
+  if constexpr (__is_same(Source, bsx_embed_gumbel)) {
+    const bsx_u32x4 u = bsx_gumbel_draws(p.sample_seed, lane, step);
+    return bsx_gumbel_select_n(l, A, p.beta, u.v);
+  }
   return bsx_embed_argmax(l, A);
 }
 
 // The action of a lane that does not reset: the greedy action, then rollout_policy's epsilon coin on block 0 of stream
 // BSX_STREAM_POLICY — with epsilon == 0 (uniform per launch) no Philox is executed.
 template <int K, int A, class HotFn>
-__device__ __forceinline__ int bsx_embed_action(const HotFn& fn, int32_t st, const bsx_embed_net_args& p, const float* s_net, int prow,
-                                                uint64_t lane, uint64_t step) {
+__device__ __forceinline__ int bsx_embed_action(bsx_embed_greedy, const HotFn& fn, int32_t st, const bsx_embed_net_args& p, const float* s_net,
+                                                int prow, uint64_t lane, uint64_t step) {
   const int best = bsx_embed_best<K, A>(fn, st, p, s_net, prow);
   uint32_t w0 = 0, w1 = 0, w2 = 0;
   if (p.epsilon > 0.0) {
@@ -158,6 +179,14 @@ __device__ __forceinline__ int bsx_embed_action(const HotFn& fn, int32_t st, con
     w0 = w.v[0]; w1 = w.v[1]; w2 = w.v[2];
   }
   return bsx_policy_select((uint32_t)best, /*resets=*/0, p.epsilon, w0, w1, w2, (uint32_t)A);
+}
+// ... and of a drawn call: the draw itself, no coin.  The action is NOT pinned behind an opaque asm as bsx_drawn_returns_body
+// pins its own: no scalar spills here without it, and an opaque action is one the compiler can no longer prove inside
+// [0, A) — deep_sea's count of invalid actions (a global atomic) would come back into the step loop.
+template <int K, int A, class HotFn>
+__device__ __forceinline__ int bsx_embed_action(bsx_embed_gumbel, const HotFn& fn, int32_t st, const bsx_embed_net_args& p, const float* s_net,
+                                                int prow, uint64_t lane, uint64_t step) {
+  return bsx_embed_best<K, A, bsx_embed_gumbel>(fn, st, p, s_net, prow, lane, step);
 }
 
 // What both bodies do before their loop: the counters, the family's own staging, the shared pair into LDS, one barrier.
@@ -195,6 +224,7 @@ template <class F>
 __device__ __forceinline__ void bsx_embed_record_body(bsx_embed_kernarg ka, typename F::fam::shared& s_fam, unsigned int* s_cnt,
                                                       float* s_net) {
   typedef typename F::fam Fam;
+  typedef typename bsx_embed_source_of<F>::type Source;
   const bsx_embed_args& k0 = bsx_embed_view(ka);
   const typename Fam::args& a0 = F::of(k0);
   bsx_embed_stage<Fam, F::A>(a0, k0.p, s_fam, s_cnt, s_net);
@@ -220,7 +250,7 @@ __device__ __forceinline__ void bsx_embed_record_body(bsx_embed_kernarg ka, type
       const int64_t oi = (int64_t)t * a.ctl.n_lanes + i;
       const bool resets = Fam::resets(st);
       int act = 0;
-      if (!resets) act = bsx_embed_action<F::K, F::A>(fn, st, kt.p, s_net, prow, lane, step);
+      if (!resets) act = bsx_embed_action<F::K, F::A>(Source(), fn, st, kt.p, s_net, prow, lane, step);
       int32_t nst; double reward;
       const int type = Fam::template advance<true>(a, s_fam, i, lane, step, st, act, nst, reward);
       st = nst;
@@ -242,6 +272,7 @@ template <class F>
 __device__ __forceinline__ void bsx_embed_returns_body(bsx_embed_kernarg ka, typename F::fam::shared& s_fam, unsigned int* s_cnt,
                                                        float* s_net) {
   typedef typename F::fam Fam;
+  typedef typename bsx_embed_source_of<F>::type Source;
   const bsx_embed_args& k0 = bsx_embed_view(ka);
   const typename Fam::args& a0 = F::of(k0);
   bsx_embed_stage<Fam, F::A>(a0, k0.p, s_fam, s_cnt, s_net);
@@ -263,7 +294,7 @@ __device__ __forceinline__ void bsx_embed_returns_body(bsx_embed_kernarg ka, typ
       const uint64_t step = step0 + (uint64_t)t;
       const bool resets = Fam::resets(st);
       int act = 0;
-      if (!resets) act = bsx_embed_action<F::K, F::A>(F::fn(a), st, kt.p, s_net, prow, lane, step);
+      if (!resets) act = bsx_embed_action<F::K, F::A>(Source(), F::fn(a), st, kt.p, s_net, prow, lane, step);
       int32_t nst; double reward;
       const int type = Fam::advance_deferred(a, s_fam, i, lane, step, st, act, nst, reward, pend);
       st = nst;
@@ -320,25 +351,63 @@ static inline int bsx_check_embed_eval_call(const bsx_call_t* call, const bsx_po
   return bsx_embed_aligned(em);
 }
 
+// The same refusals for the drawn calls (bsx_<family>_embedding_sample / _embedding_sample_evaluate): the sampled struct as a
+// greedy one whose epsilon is 0.0 for an inv_temperature that is finite and > 0 and out of range for any other — BSX_ERANGE
+// where the epsilon is refused, as in bsx_tab_softmax_stand_in.
+static inline bsx_policy_embedding_t bsx_embed_sample_stand_in(const bsx_policy_embedding_sample_t* sm) {
+  bsx_policy_embedding_t em;
+  em.w1 = sm->w1; em.w2 = sm->w2;
+  em.n_cells = sm->n_cells; em.n_hidden = sm->n_hidden; em.n_actions = sm->n_actions; em.n_policies = sm->n_policies;
+  em.policy_index = sm->policy_index;
+  em.epsilon = (__builtin_isfinite(sm->inv_temperature) && sm->inv_temperature > 0.0) ? 0.0 : 2.0;
+  em.explore_seed = sm->sample_seed;
+  em.actions_out = sm->actions_out;
+  return em;
+}
+static inline int bsx_check_embed_sample_call(const bsx_call_t* call, const bsx_policy_embedding_sample_t* sm, int32_t n_cells,
+                                              int32_t n_actions, const int32_t* state, const bsx_timestep_t& out, const double* info) {
+  if (call == nullptr || sm == nullptr) return BSX_ENULL;
+  const bsx_policy_embedding_t em = bsx_embed_sample_stand_in(sm);
+  return bsx_check_embed_call(call, &em, n_cells, n_actions, state, out, info);
+}
+static inline int bsx_check_embed_sample_eval_call(const bsx_call_t* call, const bsx_policy_embedding_sample_t* sm, int32_t n_cells,
+                                                   int32_t n_actions, const int32_t* state, const bsx_policy_eval_t& out,
+                                                   const double* info) {
+  if (call == nullptr || sm == nullptr) return BSX_ENULL;
+  const bsx_policy_embedding_t em = bsx_embed_sample_stand_in(sm);
+  return bsx_check_embed_eval_call(call, &em, n_cells, n_actions, state, out, info);
+}
+
 // What the entry points share once the family's args are in place (a.fam).
-static inline int bsx_embed_call(bsx_embed_args& a, int32_t family, const bsx_call_t* call, const bsx_policy_embedding_t* em, bool record,
-                                 int32_t* rows, const bsx_policy_eval_t& out) {
+static inline int bsx_embed_fill_and_launch(bsx_embed_args& a, int32_t family, const bsx_call_t* call, const bsx_policy_embedding_t* em,
+                                            bool record, bool drawn, double beta, int32_t* rows, const bsx_policy_eval_t& out) {
   if (bsx_blocks_of(call->n_lanes) > 0x7FFFFFFF) return BSX_EINVAL;
   a.family = family;
   a.n_steps = call->n_steps;
   a.record = record ? 1 : 0;
-  a._pad = 0;
+  a.drawn = drawn ? 1 : 0;
   a.p.w1 = em->w1;
   a.p.w2 = em->w2;
   a.p.policy_index = em->n_policies > 1 ? em->policy_index : nullptr;
   a.p.actions_out = record ? em->actions_out : nullptr;
-  a.p.epsilon = em->epsilon;
-  a.p.explore_seed = em->explore_seed;
+  a.p.epsilon = drawn ? 0.0 : em->epsilon;
+  a.p.explore_seed = drawn ? 0 : em->explore_seed;
+  a.p.beta = beta;
+  a.p.sample_seed = drawn ? em->explore_seed : 0;
   a.p.n_cells = em->n_cells; a.p.n_hidden = em->n_hidden; a.p.n_policies = em->n_policies;
   a.p.in_lds = (em->n_policies == 1 && BSX_EMBED_STAGED_BYTES(em->n_cells, em->n_hidden) <= BSX_EMBED_LDS_BYTES) ? 1 : 0;
   a.rows = rows;
   a.out = out;
   return bsx_launch_embed(a, (hipStream_t)call->hip_stream);
+}
+static inline int bsx_embed_call(bsx_embed_args& a, int32_t family, const bsx_call_t* call, const bsx_policy_embedding_t* em, bool record,
+                                 int32_t* rows, const bsx_policy_eval_t& out) {
+  return bsx_embed_fill_and_launch(a, family, call, em, record, false, 1.0, rows, out);
+}
+static inline int bsx_embed_sample_call(bsx_embed_args& a, int32_t family, const bsx_call_t* call, const bsx_policy_embedding_sample_t* sm,
+                                        bool record, int32_t* rows, const bsx_policy_eval_t& out) {
+  const bsx_policy_embedding_t em = bsx_embed_sample_stand_in(sm);
+  return bsx_embed_fill_and_launch(a, family, call, &em, record, true, sm->inv_temperature, rows, out);
 }
 
 #endif  // BSX_EMBED_DEVICE_H_

@@ -126,6 +126,32 @@ extern "C" int bsx_catch_embedding_evaluate(const bsx_catch_t* cfg, const bsx_ca
   return bsx_embed_call(s, BSX_FAM_CATCH, call, policy, false, nullptr, out);
 }
 
+extern "C" int bsx_catch_embedding_sample(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                       int32_t* state, bsx_timestep_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = catch_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_embed_sample_call(call, policy, cfg->rows * cfg->columns, 3, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_embed_args s;
+  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_catch_policy_rollout)
+  rc = catch_make(cfg, call, policy->actions_out, state, out, info, &s.fam.catch_);
+  if (rc != 0) return rc;
+  s.fam.catch_.action = nullptr;
+  return bsx_embed_sample_call(s, BSX_FAM_CATCH, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+}
+
+extern "C" int bsx_catch_embedding_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call,
+                                                const bsx_policy_embedding_sample_t* policy, int32_t* state, bsx_policy_eval_t out,
+                                                double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = catch_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_embed_sample_eval_call(call, policy, cfg->rows * cfg->columns, 3, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_embed_args s;
+  catch_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.catch_);          // (no action column, no TimeStep)
+  return bsx_embed_sample_call(s, BSX_FAM_CATCH, call, policy, false, nullptr, out);
+}
+
 extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catch_t* cfg, const bsx_call_t* call,
                                    const int32_t* action, int32_t* state, bsx_timestep_t out, double* info) {
   if (g == nullptr) return BSX_ENULL;

@@ -277,6 +277,32 @@ extern "C" int bsx_deep_sea_embedding_evaluate(const bsx_deep_sea_t* cfg, const 
   return bsx_embed_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
 }
 
+extern "C" int bsx_deep_sea_embedding_sample(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                       int32_t* state, bsx_timestep_t out, double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_embed_sample_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_embed_args s;
+  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_deep_sea_policy_rollout)
+  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &s.fam.deep_sea);
+  if (rc != 0) return rc;
+  s.fam.deep_sea.action = nullptr;
+  return bsx_embed_sample_call(s, BSX_FAM_DEEP_SEA, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+}
+
+extern "C" int bsx_deep_sea_embedding_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call,
+                                                const bsx_policy_embedding_sample_t* policy, int32_t* state, bsx_policy_eval_t out,
+                                                double* info) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = deep_sea_check_cfg(cfg);
+  if (rc == 0) rc = bsx_check_embed_sample_eval_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  bsx_embed_args s;
+  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);          // (no action column, no TimeStep)
+  return bsx_embed_sample_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
+}
+
 extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_deep_sea_t* cfg,
                                       const bsx_call_t* call, const int32_t* action, int32_t* state,
                                       bsx_timestep_t out, double* info) {

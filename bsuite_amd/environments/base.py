@@ -1119,6 +1119,84 @@ class Environment(dm_env.EnvironmentBase):
     self._launch_steps(getattr(_native.lib, self._embedding_eval_abi), args, int(num_steps), what)
     return ev
 
+  _embedding_sample_abi = None        # subclass: the C-ABI entry points of sample_embedding / evaluate_sampled_embedding
+  _embedding_sample_eval_abi = None   # (deep_sea, catch)
+
+  def _check_sample_embedding(self, w1, w2, num_steps, policy_index, temperature, sample_seed, what, abi):
+    """The refusals of sample_embedding() and evaluate_sampled_embedding() (`what`), all before any GPU use, nothing allocated:
+    _check_embedding's — the environment's part (_check_policy_env), the pair of matrices, the population rule — without an
+    epsilon, then the temperature and the seed as _check_sample_policy refuses them (_check_sample).  Returns (P, H, beta)."""
+    P, H = self._check_embedding(w1, w2, num_steps, policy_index, 0.0, 0, what, abi)
+    return P, H, self._check_sample(what, temperature, sample_seed)
+
+  def _policy_embedding_sample(self, w1, w2, P, H, policy_index, beta, sample_seed, actions):
+    return _native.PolicyEmbeddingSample(w1.data_ptr(), w2.data_ptr(), int(np.prod(self._board_shape)), H, int(self._num_actions), P,
+                                         policy_index.data_ptr() if policy_index is not None else None, beta, int(sample_seed),
+                                         actions.data_ptr() if actions is not None else None)
+
+  def sample_embedding(self, w1, w2, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`rollout_embedding` for a learner that needs actions DRAWN from its network (REINFORCE, actor-critic, PPO on deep_sea or
+    catch): a closed-loop rollout of `num_steps` steps in ONE launch, the actions drawn from softmax(logits / temperature) of
+    a network with one ReLU hidden layer whose first layer is a row gather on the lane's own index observation (DeepSea and
+    Catch, batched view, observation_mode='index', counter-based draws, no wrapper).
+
+    `w1`, `w2` and `policy_index` are rollout_embedding's: with C the cells of `board_shape`, A = action_spec().num_values and
+    H hidden units, 1 <= H <= 64, contiguous float32 device tensors [C + 2, H] and [A, H + 1], or a population [P, C + 2, H]
+    and [P, A, H + 1] with `policy_index`, int32 [B], naming each lane's pair (clamped to [0, P-1]; with one pair it must be
+    None).  Only 4-byte alignment is assumed.  Returns `(ts, actions)` as rollout_policy does and equals, bit for bit in
+    everything it returns and everything it leaves behind,
+
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(embedding_logits(w1, w2, observation before the call),
+                                             words(sample_seed, lane, call index), temperature)
+                           ts[t] = step(a); actions[t] = a
+
+    embedding_logits and gumbel_select are utils.observations': the float32 logits of rollout_embedding (every add and every
+    multiply rounded on its own, cells clamped to [-1, C-1]; csrc/bsx_embed.h), then Gumbel-max in float64 over the A logits —
+    u_a = (word_a + 0.5) * 2^-32, g_a = -log(-log(u_a)) with the engine's bit-reproducible logarithm,
+    z_a = l_a * (1 / temperature) + g_a, the largest z wins, the lowest index wins a tie, a NaN never wins and a -inf logit
+    masks its action — which draws action a with probability softmax(logits / temperature)[a].  The words are words 0..A-1 of
+    block 0 of stream 3 of (sample_seed, global lane id, call index); nothing is computed or drawn on a step that resets, and
+    the environment's own stream 0 is untouched, so `rollout(actions)` on a twin reproduces `ts`.  temperature: a finite
+    number > 0 whose inverse is finite; there is no epsilon and no greedy limit (that is rollout_embedding).
+    Log-probabilities are not outputs: a learner computes `embedding_logits` of the returned observations itself.  The 15 KiB
+    on-chip rule for a shared pair is rollout_embedding's.  State, bsuite_info(), episode_counters(), invalid_action_count()
+    and the call index are left as T step() calls leave them; calls interleave freely with step / rollout / rollout_policy /
+    sample_policy / rollout_embedding / evaluate_embedding / mark_reset / reset.  Output buffers are cached per T, shared with
+    rollout_policy(), and overwritten by the next call of the same T."""
+    what = 'sample_embedding'
+    P, H, beta = self._check_sample_embedding(w1, w2, num_steps, policy_index, temperature, sample_seed, what, '_embedding_sample_abi')
+    self._ensure_allocated()
+    T = int(num_steps)
+    if T not in self._policy_rollout_out:
+      actions = torch.empty((T, self._batch), dtype=torch.int32, device=self._device)
+      self._policy_rollout_out[T] = self._new_outputs((T, self._batch), dict(device=self._device)) + (actions,)
+    _, ptrs, timestep, actions = self._policy_rollout_out[T]
+    pol = self._policy_embedding_sample(w1, w2, P, H, policy_index, beta, sample_seed, actions)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), ptrs,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._embedding_sample_abi), args, T, what)
+    return timestep, actions
+
+  def evaluate_sampled_embedding(self, w1, w2, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`sample_embedding` with the same arguments, returns only: the lanes take the same `num_steps` steps with the same draws
+    in ONE launch, and state, bsuite_info(), episode_counters(), invalid_action_count() and the call index are left bit for bit
+    where sample_embedding leaves them, but no TimeStep is written.  Returns the cached `PolicyEvaluation` of evaluate_policy
+    — episodes int32, return_sum and episode_return_sum float64, [B] each — with the same definitions: the float64 reward of
+    the step before its rounding to float32, summed in step order (evaluate_policy has the loop).  The refusals are
+    sample_embedding's.  The three buffers are shared with evaluate_policy() and overwritten by the next call of either."""
+    what = 'evaluate_sampled_embedding'
+    P, H, beta = self._check_sample_embedding(w1, w2, num_steps, policy_index, temperature, sample_seed, what,
+                                              '_embedding_sample_eval_abi')
+    self._ensure_allocated()
+    ev = self._policy_evaluation_out()
+    pol = self._policy_embedding_sample(w1, w2, P, H, policy_index, beta, sample_seed, None)
+    out = _native.PolicyEvalPtrs(ev.episodes.data_ptr(), ev.return_sum.data_ptr(), ev.episode_return_sum.data_ptr())
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(pol), self._state['state'].data_ptr(), out,
+            self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._embedding_sample_eval_abi), args, int(num_steps), what)
+    return ev
+
   _linear_eval_abi = None   # subclass: the C-ABI entry point of evaluate_linear (cartpole, swing-up, mountain_car)
 
   def _check_fused_eval(self, what, abi, num_steps, epsilon, explore_seed):

@@ -51,6 +51,8 @@ class Catch(base.Environment):
   _policy_sample_eval_abi = 'bsx_catch_policy_sample_evaluate'
   _embedding_rollout_abi = 'bsx_catch_embedding_rollout'
   _embedding_eval_abi = 'bsx_catch_embedding_evaluate'
+  _embedding_sample_abi = 'bsx_catch_embedding_sample'
+  _embedding_sample_eval_abi = 'bsx_catch_embedding_sample_evaluate'
 
   @property
   def policy_num_states(self) -> int:

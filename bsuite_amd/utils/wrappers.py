@@ -140,6 +140,20 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'evaluate_embedding() is not available through {type(self).__name__}: the fused hidden-layer evaluation '
                      'has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
 
+  def sample_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like rollout_embedding: the sampled rollout records the raw environment's rewards
+    (base.Environment.sample_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError(f'sample_embedding() is not available through {type(self).__name__}: the fused sampled hidden-layer rollout '
+                     'has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_sampled_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like evaluate_embedding: the sampled evaluation sums the raw environment's rewards
+    (base.Environment.evaluate_sampled_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError(f'evaluate_sampled_embedding() is not available through {type(self).__name__}: the fused sampled '
+                     'hidden-layer evaluation has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
+
   def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
     """Refused, like evaluate_linear: the sampled evaluation sums the raw environment's rewards
     (base.Environment.evaluate_sampled_linear)."""
@@ -639,6 +653,20 @@ class ImageObservation(dm_env.EnvironmentBase):
     del w1, w2, num_steps, kwargs
     raise ValueError('evaluate_embedding() is not available through ImageObservation: the fused hidden-layer evaluation gathers '
                      'its first layer by index observations; call it on an un-wrapped DeepSea / Catch')
+
+  def sample_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like rollout_embedding: a fused sampled hidden-layer rollout returns index observations, never images
+    (base.Environment.sample_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError('sample_embedding() is not available through ImageObservation: the fused sampled hidden-layer rollout '
+                     'returns index observations; call it on an un-wrapped DeepSea / Catch')
+
+  def evaluate_sampled_embedding(self, w1, w2, num_steps, **kwargs):
+    """Refused, like evaluate_embedding: the fused sampled hidden-layer evaluation gathers its first layer by index observations
+    (base.Environment.evaluate_sampled_embedding)."""
+    del w1, w2, num_steps, kwargs
+    raise ValueError('evaluate_sampled_embedding() is not available through ImageObservation: the fused sampled hidden-layer '
+                     'evaluation gathers its first layer by index observations; call it on an un-wrapped DeepSea / Catch')
 
   def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
     """Refused: the sampled linear evaluation draws its actions from the raw environment's float rows, never images

@@ -431,6 +431,47 @@ int bsx_deep_sea_embedding_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t*
 int bsx_catch_embedding_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
                                  int32_t* state, bsx_policy_eval_t out, double* info);
 
+/* ---- fused sampled closed loops from a hidden-layer policy on the index row (deep_sea, catch; v12, additive) ----
+ * bsx_<family>_embedding_rollout / bsx_<family>_embedding_evaluate with the action source of bsx_<family>_policy_sample, in
+ * ONE launch of the same kernel: the network, its matrices, n_cells, n_hidden, n_actions and the clamps are those of
+ * bsx_policy_embedding_t; instead of the greedy action (and no epsilon coin) the lane takes a draw from
+ * softmax(inv_temperature * l).  Per step t and lane i:
+ *     a = 0                                        if the lane resets on this call
+ *       = argmax_c z_c                             else, with l the float32 logits of the lane's index row BEFORE the call
+ *         u_c = ((double)word_c + 0.5) * 2^-32;  g_c = -bsx_log(-bsx_log(u_c));  z_c = (double)l[c] * inv_temperature + g_c
+ *         (float64, each operation rounded on its own; c = 0 .. n_actions-1 in order, the lowest index wins a tie, a NaN
+ *         never wins, a -inf logit masks its action: csrc/bsx_embed_sample.h)
+ *     then exactly step(a).
+ * word_c = word c of block 0 of stream 3 (BSX_STREAM_SAMPLE) of (sample_seed, global lane id, the step's call index).  A
+ * lane that resets computes and draws nothing; the environment's own stream is untouched.
+ *   bsx_<family>_embedding_sample            writes what bsx_<family>_embedding_rollout writes: `out` [n_steps, n_lanes(, K)]
+ *                                            and actions_out[t * n_lanes + i] = a
+ *   bsx_<family>_embedding_sample_evaluate   takes the same steps with the same draws and writes the three columns of
+ *                                            bsx_policy_eval_t; actions_out is not looked at
+ * State, info, counters and the call index end up as n_steps step() calls leave them, the same after either call.
+ * Refusals (all before any device work), those of bsx_<family>_embedding_rollout / _embedding_evaluate in their order, with
+ * BSX_ERANGE for an inv_temperature that is not a finite number > 0 where an epsilon outside [0, 1] is refused there; last
+ * BSX_EALIGN for w1 or w2 that is not 4-byte aligned.  n_lanes == 0 returns 0 and launches nothing.  Asynchronous on
+ * call->hip_stream, no allocation, no synchronisation, graph-capturable. */
+typedef struct {
+  const float*   w1;             /* device [n_policies, n_cells + 2, n_hidden]                     */
+  const float*   w2;             /* device [n_policies, n_actions, n_hidden + 1]                   */
+  int32_t        n_cells, n_hidden, n_actions, n_policies;
+  const int32_t* policy_index;   /* device [n_lanes] or NULL when n_policies == 1                  */
+  double         inv_temperature;
+  uint64_t       sample_seed;
+  int32_t*       actions_out;    /* device [n_steps, n_lanes] (bsx_<family>_embedding_sample)      */
+} bsx_policy_embedding_sample_t;
+int bsx_deep_sea_embedding_sample(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                  int32_t* state, bsx_timestep_t out, double* info);
+int bsx_catch_embedding_sample(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                               int32_t* state, bsx_timestep_t out, double* info);
+int bsx_deep_sea_embedding_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call,
+                                           const bsx_policy_embedding_sample_t* policy, int32_t* state, bsx_policy_eval_t out,
+                                           double* info);
+int bsx_catch_embedding_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                        int32_t* state, bsx_policy_eval_t out, double* info);
+
 /* ---- bandit : bsuite/environments/bandit.py:35-73 ----------------------------------------- */
 #define BSX_BANDIT_MAX_ACTIONS 32
 typedef struct {
