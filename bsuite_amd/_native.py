@@ -157,6 +157,15 @@ class LinearEvalPtrs(ctypes.Structure):
               ('observation_out', ctypes.c_void_p)]
 
 
+class Returns(ctypes.Structure):
+  """bsx_returns_t: the trajectory columns, the parameters and the outputs of bsx_lambda_returns (`lambda` is `lambda_` here)."""
+  _fields_ = [('n_lanes', ctypes.c_int64), ('n_steps', ctypes.c_int32), ('_pad', ctypes.c_int32),
+              ('reward', ctypes.c_void_p), ('discount', ctypes.c_void_p), ('step_type', ctypes.c_void_p),
+              ('values', ctypes.c_void_p), ('bootstrap', ctypes.c_void_p),
+              ('gamma', ctypes.c_double), ('lambda_', ctypes.c_double),
+              ('returns', ctypes.c_void_p), ('td_errors', ctypes.c_void_p)]
+
+
 class BanditCfg(ctypes.Structure):
   _fields_ = [('num_actions', ctypes.c_int32), ('_pad', ctypes.c_int32),
               ('rewards', ctypes.c_double * BANDIT_MAX_ACTIONS)]
@@ -224,6 +233,7 @@ _SIGS = {
     'bsx_calib_fill': ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     'bsx_calib_copy': ([_P, _P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     'bsx_counter_add': ([_P, ctypes.c_uint64, _P], ctypes.c_int),
+    'bsx_lambda_returns': ([ctypes.POINTER(Returns), _P], ctypes.c_int),
     'bsx_image_observation': ([ctypes.POINTER(ImageCfg), ctypes.c_int64, _P, _P, _P], ctypes.c_int),
     'bsx_image_observation_typed': ([ctypes.POINTER(ImageCfg), ctypes.c_int64, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                      _P], ctypes.c_int),

@@ -917,9 +917,20 @@ static void launch_regs_rollout(const typename Env::args& a, int n_steps, int v,
 
 // LPT lanes per thread for the lean eager step of a register-resident family (Env::EAGER_LPT_MIN_BLOCKS: from this many
 // one-lane workgroups up, 0 = never; Env::EAGER_LPT)
+// (a family whose gate is 0 — cartpole: never, measured equal or slower — has the kernel in the tuning build alone, where
+// BSX_EAGER2_MIN_BLOCKS can open the gate: a kernel that can never launch still counts against the library's kernel budget)
+template <class Env>
+static constexpr bool small_obs_has_eager_lpt() {
+#ifdef BSX_TUNING
+  return Env::HAS_REGS;
+#else
+  if constexpr (Env::HAS_REGS) return Env::EAGER_LPT_MIN_BLOCKS > 0;
+  else return false;
+#endif
+}
 template <class Env, int LPT>
 static void launch_eager_lpt(const typename Env::args& a, int v, hipStream_t st) {
-  if constexpr (Env::HAS_REGS) {
+  if constexpr (small_obs_has_eager_lpt<Env>()) {
     const dim3 g((unsigned)((a.ctl.n_lanes + LPT * BSX_BLOCK - 1) / (LPT * BSX_BLOCK))), b(BSX_BLOCK);
     if (v == 1) small_obs_eager2_kernel<Env, small_obs_v1<Env>(), LPT><<<g, b, 0, st>>>(a);
     else small_obs_eager2_kernel<Env, 0, LPT><<<g, b, 0, st>>>(a);

@@ -866,6 +866,54 @@ int bsx_image_observation(const bsx_image_t* cfg, int64_t n_lanes, const float* 
 int bsx_image_observation_typed(const bsx_image_t* cfg, int64_t n_lanes, const void* obs, int32_t obs_code,
                                 void* image, int32_t image_code, void* hip_stream);
 
+/* ---- returns of a recorded trajectory (v12, additive) ---------------------------------------------
+ * lambda_returns / td_lambda: what an actor-critic learner computes from the [T,B] TimeStep of a recording call before it
+ * has a loss (the reference's baseline: bsuite/baselines/jax/actor_critic/agent.py:60-66, rlax.td_lambda) — a backward
+ * recursion over the time axis, cut at episode ends, in ONE launch.
+ * Inputs, all [T,B] row-major, T >= 1: reward f32, discount f32, step_type int8 (nullable), values f32 [T+1,B]
+ * (nullable; values[0] is V of the observation the trajectory started from, values[t+1] is V of observation[t] — rlax's
+ * v_tm1 = values[:-1], v_t = values[1:]), bootstrap f32 [B] (nullable, only without values), gamma and lambda in [0,1].
+ * Each lane i on its own, in float64, every multiply and add rounded on its own, one_minus = 1.0 - lambda computed once
+ * on the host in double:
+ *   vals(t) = values ? (double)values[t][i] : +0.0
+ *   carry   = values ? (double)values[T][i] : (bootstrap ? (double)bootstrap[i] : +0.0)
+ *   for t = T-1 .. 0:
+ *     if step_type && step_type[t][i] == BSX_FIRST:
+ *       g = vals(t)                       the row is no transition: its td error is exactly 0 ...
+ *     else:
+ *       dg  = gamma * (double)discount[t][i]
+ *       mix = one_minus * vals(t+1) + lambda * carry
+ *       g   = (double)reward[t][i] + dg * mix
+ *     carry = g                           ... and the row before it bootstraps from V of its own last observation
+ *                                             only (truncation), never from the new episode
+ *     returns[t][i]   = (float)g
+ *     td_errors[t][i] = (float)(g - vals(t))        only when requested; needs values
+ * A LAST row has discount 0, which cuts the recursion by itself; the FIRST rule adds the case the discount cannot
+ * express — a lane restarted by bsx_lane_reset_mark, or a window stitched from two calls, has a FIRST with no LAST in
+ * front of it.  lambda = 1 without values is the discounted Monte-Carlo return; with values this is rlax.lambda_returns
+ * and td_errors is rlax.td_lambda on the rows that are transitions.  "Values absent" is the arithmetic above with +0.0,
+ * additions included (skipping them would change the sign of zero results, e.g. for a reward of -0.0).
+ * Pointers need 4-byte alignment only.  Asynchronous on hip_stream, no allocation, no synchronisation, graph-capturable;
+ * an output may not overlap an input.  Checks, in this order and before any device work: r NULL -> BSX_ENULL;
+ * n_steps < 1, n_lanes < 0 or n_lanes > 2^40 -> BSX_EINVAL; gamma or lambda outside [0,1], NaN included -> BSX_ERANGE;
+ * bootstrap together with values, or td_errors without values -> BSX_EMODE; n_lanes == 0 -> 0; reward or discount NULL,
+ * or both outputs NULL -> BSX_ENULL; more lanes than one grid of 256-thread workgroups holds, or (n_steps + 1) * n_lanes
+ * elements beyond 64-bit byte offsets -> BSX_EINVAL. */
+typedef struct {
+  int64_t n_lanes;
+  int32_t n_steps;
+  int32_t _pad;
+  const float* reward;        /* [T,B]                      */
+  const float* discount;      /* [T,B]                      */
+  const int8_t* step_type;    /* [T,B], nullable            */
+  const float* values;        /* [T+1,B], nullable          */
+  const float* bootstrap;     /* [B], nullable              */
+  double gamma, lambda;
+  float* returns;             /* [T,B], nullable            */
+  float* td_errors;           /* [T,B], nullable            */
+} bsx_returns_t;
+int bsx_lambda_returns(const bsx_returns_t* r, void* hip_stream);
+
 /* ---- misc ---------------------------------------------------------------------------------- */
 int bsx_abi_version(void);
 /* bsuite_info() through the C ABI (v12): info_out [n_info, B] = the family's info columns as the REFERENCE would report
