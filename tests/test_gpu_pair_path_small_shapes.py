@@ -23,8 +23,8 @@ def test_pair_path_parity_at_small_shapes():
   env = dict(os.environ, BSX_NATIVE_LIB=_build.build(tuning=True), BSX_FUSED_TILE_MAX_CELLS='0', BSX_DEEP_SEA_STEP1='0', PYTHONPATH=ROOT)
   p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
                       'tests/test_gpu_golden.py', 'tests/test_gpu_oracle_batch.py', 'tests/test_gpu_rollout.py',
-                      'tests/test_gpu_delta_obs.py', 'tests/test_gpu_engine_features.py',
-                      '-k', 'deep_sea or catch or pipelined or delta or engine'],
+                      'tests/test_gpu_delta_obs.py', 'tests/test_gpu_engine_features.py', 'tests/test_gpu_grid_edges.py',
+                      '-k', '(deep_sea or catch or pipelined or delta or engine) and not several_folds and not large_batch'],
                      cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1100)
   tail = p.stdout[-3000:]
   assert p.returncode == 0, tail
@@ -40,7 +40,8 @@ def test_256_lane_fused_tiles_at_small_shapes():
   env = dict(os.environ, BSX_NATIVE_LIB=_build.build(tuning=True), BSX_FUSED_TILE64_MAX_LANES='0', PYTHONPATH=ROOT)
   p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
                       'tests/test_gpu_golden.py', 'tests/test_gpu_oracle_batch.py', 'tests/test_gpu_engine_features.py',
-                      '-k', 'deep_sea or catch or engine'],
+                      'tests/test_gpu_grid_edges.py',
+                      '-k', '(deep_sea or catch or engine) and not several_folds and not large_batch'],
                      cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=800)
   tail = p.stdout[-3000:]
   assert p.returncode == 0, tail
@@ -58,7 +59,8 @@ def test_two_lanes_per_thread_advance_at_small_shapes():
              BSX_DEEP_SEA_STEP1='0', PYTHONPATH=ROOT)
   p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
                       'tests/test_gpu_golden.py', 'tests/test_gpu_oracle_batch.py', 'tests/test_gpu_engine_features.py',
-                      '-k', 'deep_sea or catch or mnist or engine'],
+                      'tests/test_gpu_grid_edges.py',
+                      '-k', '(deep_sea or catch or mnist or engine) and not several_folds and not large_batch'],
                      cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=800)
   tail = p.stdout[-3000:]
   assert p.returncode == 0, tail

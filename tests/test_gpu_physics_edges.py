@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from bsuite_amd.utils import wrappers
+from tests import edge_snap_util as es
 from tests import engine_util as eu
 from tests import physics_edge_util as pu
 from tests import policy_eval_util as pe
@@ -27,6 +28,7 @@ pytestmark = pytest.mark.gpu
 CASES = list(zip(pu.CASES, pu.CASE_IDS))
 CASE_PARAMS = [pytest.param(f, kw, id=i) for (f, kw), i in CASES]
 T_MAX = 3
+_bits, _snap_ts, _snap_after, _stack, _assert_ts, _assert_after = es.bits, es.snap_ts, es.snap_after, es.stack, es.assert_ts, es.assert_after
 
 # Measured on the MI355X by test_eager_step_against_the_oracle itself (it prints the table per component):
 # max |a-b| / max(1,|b|) over the continuous observation components of the rows of each theta_dot band (bands 1..3 of
@@ -51,23 +53,6 @@ def band_bound(family, band):
 
 def _make(family, kwargs, batch, **engine_kwargs):
   return eu.make_env(family, dict(kwargs), batch=batch, lane_offset=pu.LANE_OFFSET, seed=pu.SEED, **engine_kwargs)
-
-
-def _bits(t):
-  if not t.is_floating_point():
-    return t
-  return t.contiguous().view(torch.int64 if t.dtype is torch.float64 else torch.int32)
-
-
-def _snap_ts(ts):
-  return {f: _bits(getattr(ts, f)).clone() for f in ('step_type', 'reward', 'discount', 'observation')}
-
-
-def _snap_after(env):
-  r = eu.raw(env)
-  return dict(state={k: _bits(v).clone() for k, v in r._state.items()},          # pylint: disable=protected-access
-              info={k: _bits(v).clone() for k, v in r.bsuite_info().items()},
-              counters=r.episode_counters().clone(), step_index=r.step_index)
 
 
 def _actions(g, T):
@@ -98,34 +83,6 @@ def eager(family, kwargs):
       after.append(_snap_after(env))
     _EAGER[key] = dict(ts=ts, after=after, actions=acts)
   return _EAGER[key]
-
-
-def _assert_ts(got, want, what, fields=('step_type', 'reward', 'discount', 'observation'), rows=None):
-  stacked = want['step_type'].dim() == 2                                        # [T, B, ...] of a rollout, else [B, ...]
-  for f in fields:
-    w = want[f] if rows is None else want[f][rows]
-    if not torch.equal(got[f], w):
-      d = (got[f] != w).movedim(1, 0) if stacked else got[f] != w
-      bad = d.reshape(d.shape[0], -1).any(dim=1).nonzero().flatten()
-      raise AssertionError(f'{what}: {f} differs from the eager step on {len(bad)} lanes, first {bad[:8].tolist()}')
-
-
-def _assert_after(got, want, what, info=True, rows=None):
-  for k, w in want['state'].items():
-    w = w if rows is None else w[..., rows]
-    if not torch.equal(got['state'][k], w):
-      bad = (got['state'][k] != w).reshape(-1, w.shape[-1]).any(dim=0).nonzero().flatten()
-      raise AssertionError(f'{what}: state column {k!r} differs from the eager step on {len(bad)} lanes, first {bad[:8].tolist()}')
-  if info:
-    for k, w in want['info'].items():
-      assert torch.equal(got['info'][k], w if rows is None else w[rows]), (what, 'bsuite_info', k)
-  if rows is None:
-    assert torch.equal(got['counters'], want['counters']), (what, 'episode_counters', got['counters'].tolist(), want['counters'].tolist())
-  assert got['step_index'] == want['step_index'], (what, 'call index')
-
-
-def _stack(snaps, T):
-  return {f: torch.stack([s[f] for s in snaps[:T]]) for f in snaps[0]}
 
 
 # ------------------------------------------------------------------------------------- A. the eager step and the reference
