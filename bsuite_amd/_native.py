@@ -150,6 +150,13 @@ class Mlp(ctypes.Structure):
               ('observation_in', ctypes.c_void_p)]
 
 
+class Mlp2(ctypes.Structure):
+  """bsx_mlp2_t: the two-hidden-layer policy of bsx_<family>_mlp2_evaluate / bsx_<family>_mlp2_rollout."""
+  _fields_ = [('w1', ctypes.c_void_p), ('w2', ctypes.c_void_p), ('w3', ctypes.c_void_p), ('hidden1', ctypes.c_int32),
+              ('hidden2', ctypes.c_int32), ('n_policies', ctypes.c_int32), ('policy_index', ctypes.c_void_p),
+              ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64), ('observation_in', ctypes.c_void_p)]
+
+
 class LinearEvalPtrs(ctypes.Structure):
   """bsx_linear_eval_t: the three output columns and the final observation rows of bsx_<family>_linear_evaluate and
   bsx_<family>_mlp_evaluate."""
@@ -312,6 +319,11 @@ for _fam, _cfg in (('cartpole', CartpoleCfg), ('mountain_car', MountainCarCfg)):
     # evaluate_sampled_linear / evaluate_sampled_mlp: the evaluation's arguments with `double inv_temperature` after the struct
     _SIGS[f'bsx_{_fam}_{_kind}_sample_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy),
                                                      ctypes.c_double, _P, _P, LinearEvalPtrs, _P], ctypes.c_int)
+  # evaluate_mlp2 / rollout_mlp2: the signatures of *_mlp_evaluate / *_mlp_rollout with the triple of matrices
+  _SIGS[f'bsx_{_fam}_mlp2_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), _P, _P,
+                                         LinearEvalPtrs, _P], ctypes.c_int)
+  _SIGS[f'bsx_{_fam}_mlp2_rollout'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), _P, _P,
+                                        TimeStepPtrs, _P, _P], ctypes.c_int)
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({
     'bsx_group_create': ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_G)], ctypes.c_int),

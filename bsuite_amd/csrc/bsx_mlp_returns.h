@@ -61,6 +61,8 @@ struct bsx_mlp_mountain_car {
 //           bsx_policy_clamp(policy_index[i], P) alone, so a wave whose lanes name one pair touches one line per load and
 //           a wave of 64 different pairs touches 64 (the caller's layout: lanes grouped by policy is the fast one).
 // The arguments are read through three views (bsx_mlp_view): one before the loop, one per step, one after the loop.
+// (bsx_torso_body, bsx_torso.h, repeats this loop's skeleton around a two-hidden-layer policy: a change to the prologue, the
+// coin, the n_first rule or the epilogue here belongs there too.)
 template <class Fam, int V, bool SHARED>
 __device__ __forceinline__ void bsx_mlp_returns_body(bsx_mlp_kernarg ka, float* s_w, unsigned int* s_cnt) {
   typedef typename Fam::env Env;

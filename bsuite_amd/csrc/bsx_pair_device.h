@@ -88,11 +88,19 @@ __device__ __forceinline__ void bsx_advance_body(const typename Fam::args& a, ui
   bsx_flush_counts(a.ctl, s_cnt, block_id);
 }
 
+// (A family with Fam::ADVANCE_WITHOUT_MT == false — deep_sea — has no <Fam, false, 0> kernel of its own: its wrapped kernel
+// <Fam, false, -1> holds BOTH bodies and takes one uniform branch on ctl.mt_state per launch, so that a wrapped call on the
+// counter-based stream runs the body with the MT19937-exact generators compiled out, as it did from its own kernel.)
 template <class Fam, bool LEAN = false, int MT = -1>
 __global__ void __launch_bounds__(BSX_BLOCK) bsx_advance_kernel(const typename Fam::args a) {
   __shared__ typename Fam::shared s_fam;
   __shared__ unsigned int s_cnt[2];
-  bsx_advance_body<Fam, LEAN, MT>(a, blockIdx.x, s_fam, s_cnt);
+  if constexpr (!LEAN && MT == -1 && !Fam::ADVANCE_WITHOUT_MT) {
+    if (a.ctl.mt_state == nullptr) bsx_advance_body<Fam, false, 0>(a, blockIdx.x, s_fam, s_cnt);
+    else bsx_advance_body<Fam, false, -1>(a, blockIdx.x, s_fam, s_cnt);
+  } else {
+    bsx_advance_body<Fam, LEAN, MT>(a, blockIdx.x, s_fam, s_cnt);
+  }
 }
 // (the WRAPPED call with two lanes per thread — Logging / RewardNoise instantiation — measured in round 6 and not kept:
 // catch_noise/0 49.4-50.0 -> 51.4-51.7 us per step, its normal draws then run twice in series; deep_sea under Logging equal;

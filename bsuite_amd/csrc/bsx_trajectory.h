@@ -109,6 +109,8 @@ __device__ __forceinline__ void bsx_trajectory_store_row(BSX_GLOBAL float* dst, 
 //   HIDDEN  one ReLU hidden layer of p.hidden units (bsx_mlp.h), else a linear map (bsx_linear.h).
 // The arguments are read through three views (bsx_trajectory_view): one before the loop, one per step, one after the loop.
 // No barrier, no atomic and no LDS write inside the loop.
+// (bsx_torso_body, bsx_torso.h, repeats this loop's skeleton — prologue, coin, per-step stores, the n_first rule, epilogue —
+// around a two-hidden-layer policy: a change to any of them here belongs there too.)
 template <class Fam, int V, bool SHARED, bool HIDDEN>
 __device__ __forceinline__ void bsx_trajectory_body(bsx_trajectory_kernarg ka, float* s_w, unsigned int* s_cnt) {
   typedef typename Fam::env Env;

@@ -18,6 +18,7 @@
 #define CATCH_PENDING_MAX 127
 
 struct catch_fam {
+  static constexpr bool ADVANCE_WITHOUT_MT = true;     // (bsx_launch_advance)
   struct args {
     bsx_ctl ctl;
     const int32_t* action;

@@ -16,6 +16,9 @@
 #define DS_MAP_WORDS (BSX_DEEP_SEA_MAX_SIZE * BSX_DEEP_SEA_MAX_SIZE / 32)
 
 struct deep_sea_fam {
+  // No kernel of its own for the wrapped lane advance on counter-based draws: the wrapped kernel holds that body beside
+  // the MT19937-exact one, a uniform switch per launch (bsx_advance_kernel; catch keeps the separate kernel).
+  static constexpr bool ADVANCE_WITHOUT_MT = false;
   struct args {
     bsx_ctl ctl;
     const int32_t* action;

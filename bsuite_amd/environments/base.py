@@ -1429,6 +1429,96 @@ class Environment(dm_env.EnvironmentBase):
     self._launch_steps(getattr(_native.lib, self._mlp_rollout_abi), args, T, what)
     return timestep, actions
 
+  _mlp2_eval_abi = None        # subclass: the C-ABI entry points of evaluate_mlp2 / rollout_mlp2 (cartpole, swing-up,
+  _mlp2_rollout_abi = None     # mountain_car)
+
+  def _check_evaluate_mlp2(self, w1, w2, w3, observation, num_steps, policy_index, epsilon, explore_seed, what='evaluate_mlp2',
+                           abi='_mlp2_eval_abi'):
+    """The refusals of evaluate_mlp2() and rollout_mlp2() (`what`; `abi` names the attribute that holds its entry point): all
+    of them before any GPU use, nothing allocated.  Returns (P, H1, H2)."""
+    self._check_fused_eval(what, getattr(self, abi), num_steps, epsilon, explore_seed)
+    A, D, Hmax = self._num_actions, int(np.prod(self._obs_shape)), _native.MLP_MAX_HIDDEN
+    H1 = int(w1.shape[-2]) if torch.is_tensor(w1) and w1.dim() in (2, 3) else 0
+    if not 1 <= H1 <= Hmax or not self._is_eval_weight(w1, (2, 3), (H1, D + 1)):
+      raise ValueError(f'{what}: w1 must be a contiguous float32 tensor of shape (H1, {D + 1}) or (P, H1, {D + 1}) on {self._device} '
+                       f'with 1 <= H1 <= {Hmax} hidden units (column {D} is the bias)')
+    lead = '' if w1.dim() == 2 else f'{int(w1.shape[0])}, '
+    same_p = lambda w: w1.dim() == 2 or int(w.shape[0]) == int(w1.shape[0])   # pylint: disable=unnecessary-lambda-assignment
+    H2 = int(w2.shape[-2]) if torch.is_tensor(w2) and w2.dim() == w1.dim() else 0
+    if not 1 <= H2 <= Hmax or not self._is_eval_weight(w2, (w1.dim(),), (H2, H1 + 1)) or not same_p(w2):
+      raise ValueError(f'{what}: w2 must be a contiguous float32 tensor of shape ({lead}H2, {H1 + 1}) on {self._device} with '
+                       f'1 <= H2 <= {Hmax} hidden units, the same population as w1 and its hidden width (column {H1} is the bias)')
+    if not self._is_eval_weight(w3, (w1.dim(),), (A, H2 + 1)) or not same_p(w3):
+      raise ValueError(f'{what}: w3 must be a contiguous float32 tensor of shape ({lead}{A}, {H2 + 1}) on {self._device}, the '
+                       f'same population as w1 and the hidden width of w2 (column {H2} is the bias)')
+    P = 1 if w1.dim() == 2 else int(w1.shape[0])
+    return self._check_fused_eval_rows(what, observation, P, policy_index, 'weight triples', 'triple'), H1, H2
+
+  def _mlp2_struct(self, w1, w2, w3, H1, H2, P, policy_index, epsilon, explore_seed, observation):
+    return _native.Mlp2(w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), H1, H2, P,
+                        policy_index.data_ptr() if policy_index is not None else None, float(epsilon), int(explore_seed),
+                        observation.data_ptr())
+
+  def evaluate_mlp2(self, w1, w2, w3, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`evaluate_mlp` for an agent with TWO ReLU hidden layers — the shape of the reference agents' networks
+    (`MLP([64, 64])` plus a head): the same ONE launch, the same contract, result type and refusals, with another greedy
+    action.  The call equals, bit for bit in everything it leaves behind and returns,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else mlp2_select(w1[row], w2[row], w3[row], obs)
+                           ts = step(a); obs = ts.observation
+
+    w1: float32 device tensor [H1, D+1] (one triple for all lanes) or [P, H1, D+1]; w2: [H2, H1+1] or [P, H2, H1+1]; w3:
+    [3, H2+1] or [P, 3, H2+1] — the same P, 1 <= H1, H2 <= 64, the bias in the last column of each: the layout is
+    `torch.cat([lin.weight, lin.bias[:, None]], 1)` of a `torch.nn.Linear`.  With a population, `policy_index` (int32 [B],
+    clamped to [0, P-1]) names each lane's triple; with 2-D weights it must be None.  mlp2_select is
+    utils.observations.mlp2_select: h1_j = relu(w1[j][D] + sum_d w1[j][d] * obs[d]), s2_k = w2[k][H1] + sum_j w2[k][j] * h1_j
+    (j ascending), h2_k = relu(s2_k), l_a = w3[a][H2] + sum_k w3[a][k] * h2_k — float32, every multiply and add rounded on its
+    own, relu(s) = s if s > 0 else +0.0 (a NaN pre-activation gives 0); the largest logit wins, the lowest index wins a tie,
+    a NaN never wins.  epsilon, explore_seed, `observation` and the returned `LinearEvaluation` are evaluate_linear's; the
+    result buffers are the ones evaluate_linear / evaluate_mlp use, so `.observation` of any of them may be passed into any.
+    A shared triple is kept on chip.  A population is read from device memory by every lane on every step: group the lanes
+    by policy (policy_index non-decreasing) — the lanes of a wave then share their loads; a shuffled policy_index is legal
+    and slower.  State, bsuite_info(), episode_counters() and the call index are left as T step() calls with the same
+    actions leave them; calls interleave freely with step / rollout / evaluate_* / rollout_* / mark_reset / reset."""
+    P, H1, H2 = self._check_evaluate_mlp2(w1, w2, w3, observation, num_steps, policy_index, epsilon, explore_seed)
+    self._ensure_allocated()
+    ev, out = self._fused_eval_out()
+    mlp2 = self._mlp2_struct(w1, w2, w3, H1, H2, P, policy_index, epsilon, explore_seed, observation)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp2)) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp2_eval_abi), args, int(num_steps), 'evaluate_mlp2')
+    return ev
+
+  def rollout_mlp2(self, w1, w2, w3, observation, num_steps, *, policy_index=None, epsilon=0.0, explore_seed=0):
+    """`rollout_mlp` for an agent with TWO ReLU hidden layers — `evaluate_mlp2` with the same arguments, recorded: the same
+    ONE launch, the same `(ts, actions)`, contract and refusals as rollout_mlp, with another greedy action.  The call equals,
+    bit for bit in everything it returns and everything it leaves behind,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else mlp2_select(w1[row], w2[row], w3[row], obs)
+                           ts[t] = step(a); actions[t] = a; obs = ts[t].observation
+
+    w1: float32 device tensor [H1, D+1] or [P, H1, D+1]; w2: [H2, H1+1] or [P, H2, H1+1]; w3: [3, H2+1] or [P, 3, H2+1],
+    1 <= H1, H2 <= 64, each `torch.cat([lin.weight, lin.bias[:, None]], 1)` of a `torch.nn.Linear`; `policy_index`, epsilon,
+    explore_seed and `observation` as in evaluate_mlp2 (utils.observations.mlp2_select has the rule).  A shared triple is kept
+    on chip; a population is read from device memory by every lane on every step: group the lanes by policy.
+    `rollout(actions)` on a twin reproduces `ts`; a twin's evaluate_mlp2() with the same arguments ends in the same state
+    with `.observation == ts.observation[-1]` and `.episodes == (ts.step_type == LAST).sum(0)`.  Output buffers are cached
+    per T, shared with rollout_linear() and rollout_mlp(), and overwritten by the next call of the same T."""
+    what = 'rollout_mlp2'
+    P, H1, H2 = self._check_evaluate_mlp2(w1, w2, w3, observation, num_steps, policy_index, epsilon, explore_seed, what=what,
+                                          abi='_mlp2_rollout_abi')
+    self._check_trajectory_slab(what)
+    self._ensure_allocated()
+    T = int(num_steps)
+    _, ptrs, timestep, actions = self._trajectory_out(T)
+    mlp2 = self._mlp2_struct(w1, w2, w3, H1, H2, P, policy_index, epsilon, explore_seed, observation)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp2)) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp2_rollout_abi), args, T, what)
+    return timestep, actions
+
   _linear_sample_abi = None    # subclass: the C-ABI entry points of sample_linear / sample_mlp (cartpole, swing-up,
   _mlp_sample_abi = None       # mountain_car)
 

@@ -74,6 +74,8 @@ class _CartpoleBase(base.Environment):
   _mlp_eval_abi = 'bsx_cartpole_mlp_evaluate'
   _linear_rollout_abi = 'bsx_cartpole_linear_rollout'
   _mlp_rollout_abi = 'bsx_cartpole_mlp_rollout'
+  _mlp2_eval_abi = 'bsx_cartpole_mlp2_evaluate'
+  _mlp2_rollout_abi = 'bsx_cartpole_mlp2_rollout'
   _linear_sample_abi = 'bsx_cartpole_linear_sample'
   _mlp_sample_abi = 'bsx_cartpole_mlp_sample'
   _linear_sample_eval_abi = 'bsx_cartpole_linear_sample_evaluate'

@@ -32,6 +32,8 @@ class MountainCar(base.Environment):
   _mlp_eval_abi = 'bsx_mountain_car_mlp_evaluate'
   _linear_rollout_abi = 'bsx_mountain_car_linear_rollout'
   _mlp_rollout_abi = 'bsx_mountain_car_mlp_rollout'
+  _mlp2_eval_abi = 'bsx_mountain_car_mlp2_evaluate'
+  _mlp2_rollout_abi = 'bsx_mountain_car_mlp2_rollout'
   _linear_sample_abi = 'bsx_mountain_car_linear_sample'
   _mlp_sample_abi = 'bsx_mountain_car_mlp_sample'
   _linear_sample_eval_abi = 'bsx_mountain_car_linear_sample_evaluate'

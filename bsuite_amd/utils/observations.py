@@ -217,6 +217,60 @@ def mlp_logits(w1: torch.Tensor, w2: torch.Tensor, obs: torch.Tensor) -> torch.T
   return logits
 
 
+def _mlp2_forward(w1, w2, w3, obs):
+  """(logits [B, 3], s1 [B, H1], s2 [B, H2]) of the two-hidden-layer rule: `mlp2_logits` has the definition."""
+  o = obs.reshape(obs.shape[0], -1)
+  B, D = int(o.shape[0]), int(o.shape[1])
+  a1, a2, a3 = (w if w.dim() == 3 else w.unsqueeze(0).expand(B, -1, -1) for w in (w1, w2, w3))
+  H1, H2 = int(a1.shape[1]), int(a2.shape[1])
+  s1 = a1[:, :, D].clone()                                   # [B, H1]: all units of a layer at once, each in its own order
+  for d in range(D):
+    prod = a1[:, :, d] * o[:, d:d + 1]
+    s1 = s1 + prod
+  h1 = torch.where(s1 > 0, s1, torch.zeros_like(s1))
+  s2 = a2[:, :, H1].clone()                                  # [B, H2]
+  for j in range(H1):
+    prod = a2[:, :, j] * h1[:, j:j + 1]
+    s2 = s2 + prod
+  h2 = torch.where(s2 > 0, s2, torch.zeros_like(s2))
+  logits = a3[:, :, H2].clone()
+  for k in range(H2):
+    prod = a3[:, :, k] * h2[:, k:k + 1]
+    logits = logits + prod
+  return logits, s1, s2
+
+
+def mlp2_logits(w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, obs: torch.Tensor) -> torch.Tensor:
+  """The logits `[B, 3]` (float32) of a policy with two ReLU hidden layers, exactly as `env.evaluate_mlp2` / `env.rollout_mlp2`
+  compute them inside their kernel (csrc/bsx_mlp2.h):
+
+    h1_j = s if s > 0 else +0.0, s = w1[j][D]; for d = 0..D-1: s = s + w1[j][d] * obs[d]          float32, every multiply and
+    s2_k = w2[k][H1]; for j = 0..H1-1: s2_k = s2_k + w2[k][j] * h1_j                               every add rounded on its own:
+    h2_k = s2_k if s2_k > 0 else +0.0                                                              separate torch ops, never
+    l_a  = w3[a][H2]; for k = 0..H2-1: l_a = l_a + w3[a][k] * h2_k                                 addcmul or matmul
+
+  `w1` is float32 `[H1, D+1]`, `w2` `[H2, H1+1]` and `w3` `[3, H2+1]` (one triple), or `[B, H1, D+1]`, `[B, H2, H1+1]` and
+  `[B, 3, H2+1]` (lane b's own triple, e.g. `population[policy_index.clamp(0, P - 1).long()]`), the bias in the last column of
+  each: `torch.cat([lin.weight, lin.bias[:, None]], 1)` of a `torch.nn.Linear`.  A NaN pre-activation gives an activation of
+  0; `inf * 0` gives a NaN."""
+  return _mlp2_forward(w1, w2, w3, obs)[0]
+
+
+def mlp2_select(w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, obs: torch.Tensor, return_preactivations: bool = False):
+  """The greedy action `[B]` (int32) of a policy with two ReLU hidden layers on float observations, exactly as
+  `env.evaluate_mlp2` / `env.rollout_mlp2` select it inside their kernel (csrc/bsx_mlp2.h): the argmax of `mlp2_logits` (which
+  has the shapes and the rule) — the lowest index wins a tie, a NaN never wins.  With `return_preactivations` the result is
+  `(best, s1 [B, H1], s2 [B, H2])`."""
+  logits, s1, s2 = _mlp2_forward(w1, w2, w3, obs)
+  best = torch.zeros(logits.shape[0], dtype=torch.int32, device=logits.device)
+  l_best = logits[:, 0]
+  for a in range(1, int(logits.shape[1])):
+    better = logits[:, a] > l_best
+    best = torch.where(better, torch.full_like(best, a), best)
+    l_best = torch.where(better, logits[:, a], l_best)
+  return (best, s1, s2) if return_preactivations else best
+
+
 def _stream_log(x: torch.Tensor) -> torch.Tensor:
   """bsx_log (include/bsx_stream.h) on a float64 tensor of positive normal numbers, operation for operation: the exponent
   and the mantissa from the bits, m in [~0.707, 1.414], s = (m - 1) / (m + 1), the odd series of 2 atanh(s) to s^25 by

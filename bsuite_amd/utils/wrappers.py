@@ -102,6 +102,18 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'rollout_mlp() is not available through {type(self).__name__}: the fused hidden-layer rollout has no '
                      'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
+  def evaluate_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused, like evaluate_mlp: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError(f'evaluate_mlp2() is not available through {type(self).__name__}: the fused two-hidden-layer evaluation has '
+                     'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def rollout_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused, like rollout_mlp: the fused trajectory records the raw environment's rewards (base.Environment.rollout_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError(f'rollout_mlp2() is not available through {type(self).__name__}: the fused two-hidden-layer rollout has no '
+                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
   def sample_linear(self, weights, observation, num_steps, **kwargs):
     """Refused, like rollout_linear: the sampled trajectory records the raw environment's rewards (base.Environment.sample_linear)."""
     del weights, observation, num_steps, kwargs
@@ -612,6 +624,20 @@ class ImageObservation(dm_env.EnvironmentBase):
     """Refused: the fused hidden-layer rollout returns the raw environment's float rows, never images (base.Environment.rollout_mlp)."""
     del w1, w2, observation, num_steps, kwargs
     raise ValueError('rollout_mlp() is not available through ImageObservation: the fused hidden-layer rollout selects its actions '
+                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def evaluate_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused: the fused two-hidden-layer evaluation reads the raw environment's float rows, never images
+    (base.Environment.evaluate_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError('evaluate_mlp2() is not available through ImageObservation: the fused two-hidden-layer evaluation selects its '
+                     'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def rollout_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused: the fused two-hidden-layer rollout returns the raw environment's float rows, never images
+    (base.Environment.rollout_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError('rollout_mlp2() is not available through ImageObservation: the fused two-hidden-layer rollout selects its actions '
                      'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
   def sample_linear(self, weights, observation, num_steps, **kwargs):

@@ -705,6 +705,41 @@ int bsx_mountain_car_mlp_sample_evaluate(const bsx_mountain_car_t* cfg, const bs
                                          double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
                                          double* info);
 
+/* ---- two hidden layers: the greedy evaluation and its recording call from a policy with two ReLU hidden layers (cartpole,
+ *      swing-up, mountain_car; v12, additive) ------------------------------------------------------
+ * bsx_<family>_mlp_evaluate / bsx_<family>_mlp_rollout with another greedy action; everything else — the reset rule, the
+ * epsilon draws, the outputs, what is left behind, the refusals and their order, the 4 GiB slab of the recording call — is as
+ * stated above.  With H1 = hidden1, H2 = hidden2, w1 = [H1][D + 1], w2 = [H2][H1 + 1] and w3 = [3][H2 + 1] (the bias in the
+ * last column of each: the layout of a torch.nn.Linear's weight with its bias appended as a column), the greedy action of
+ * row o is
+ *     h1_j = (s > 0.0f) ? s : 0.0f with s = w1[j][D]; for d = 0 .. D-1: s = s + w1[j][d] * o[d]       j = 0 .. H1-1
+ *     s2_k = w2[k][H1];  for j = 0 .. H1-1: s2_k = s2_k + w2[k][j] * h1_j                             k = 0 .. H2-1
+ *     h2_k = (s2_k > 0.0f) ? s2_k : 0.0f             (ReLU: a NaN and a -0.0 pre-activation give +0.0; inf * 0 is a NaN)
+ *     l_a  = w3[a][H2];  for k = 0 .. H2-1: l_a = l_a + w3[a][k] * h2_k                               a = 0 .. 2
+ *     argmax_a l_a, the lowest index wins a tie and a NaN never wins
+ * in float32, every multiply and every add rounded on its own (no FMA); for a fixed k the sum runs over j ascending
+ * (csrc/bsx_mlp2.h).  Lane i takes triple row(i) of w1, w2 and w3, row(i) as for bsx_linear_t.  A shared triple is kept on
+ * chip; a population is read from global memory by every lane on every step: lanes grouped by policy share their loads.
+ * BSX_EINVAL also for hidden1 or hidden2 outside [1, 64] (reported where bsx_mlp_t's hidden is); BSX_ENULL also for w3. */
+typedef struct {
+  const float* w1;              /* device [n_policies, hidden1, D + 1], column D is the bias             */
+  const float* w2;              /* device [n_policies, hidden2, hidden1 + 1], column hidden1 is the bias */
+  const float* w3;              /* device [n_policies, 3, hidden2 + 1], column hidden2 is the bias       */
+  int32_t hidden1, hidden2;
+  int32_t n_policies;
+  const int32_t* policy_index;  /* device [n_lanes], needed iff n_policies > 1                           */
+  double epsilon; uint64_t explore_seed;
+  const float* observation_in;  /* device [n_lanes, D]: the observation of the last TimeStep             */
+} bsx_mlp2_t;
+int bsx_cartpole_mlp2_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                               float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
+int bsx_mountain_car_mlp2_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                   float* state, int32_t* steps, bsx_linear_eval_t out, double* info);
+int bsx_cartpole_mlp2_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                              float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
+int bsx_mountain_car_mlp2_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                  float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */
