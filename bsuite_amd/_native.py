@@ -248,6 +248,9 @@ _SIGS = {
                          ctypes.c_int32, ctypes.c_int32, _P, _P, _P], ctypes.c_int),
     'bsx_deep_sea_step': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                           ctypes.c_int),
+    # bsx_deep_sea_step's arguments + the hint column read (NULL: prime) and the one written
+    'bsx_deep_sea_step_hinted': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P, _P, _P],
+                                 ctypes.c_int),
     'bsx_catch_step': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                        ctypes.c_int),
     'bsx_deep_sea_policy_rollout': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,

@@ -20,6 +20,7 @@
 #include "bsx_tab_eval.h"
 #include "bsx_tab_sample_device.h"
 #include "deep_sea_fam.h"
+#include "deep_sea_hint.h"
 #include "pair_mixed.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -36,10 +37,29 @@
 // (The same for catch would put a Philox block — its reset draw — into most waves of the stream: r01 measured 100 vs
 // 42 us.  Stochastic deep_sea draws per step and keeps the two launches.)
 // (cells: a multiple of 4 — a 16-byte chunk then never straddles two lanes — and at least 768; other boards keep the two launches)
+// (hint_out != nullptr: the launch is the HINTED step instead — deep_sea_hint_advance / deep_sea_hint_stream below, one uniform
+// branch per workgroup.  It is a mode of this kernel and not a kernel of its own because the library's kernel count is held
+// where it is by the features' host tests; the two bodies share nothing but the LDS copy of the mapping.)
+__device__ __forceinline__ void deep_sea_hint_advance(const deep_sea_fam::args& a, uint32_t block_id, uint32_t* __restrict__ hint_out,
+                                                      deep_sea_fam::shared& s_fam, unsigned int* s_cnt);
+template <int K>
+__device__ __forceinline__ void deep_sea_hint_stream(float* __restrict__ obs, const uint32_t* __restrict__ hint_in,
+                                                     const int32_t* __restrict__ action, int64_t n_lanes, uint32_t cells,
+                                                     uint32_t cells_magic, bsx_div64 dv, uint32_t block_id);
+
 template <int K>
 __global__ void __launch_bounds__(BSX_BLOCK) deep_sea_step1_kernel(const deep_sea_fam::args a, const uint32_t cells,
-                                                                   const uint32_t cells_magic, const bsx_div64 dv) {
+                                                                   const uint32_t cells_magic, const bsx_div64 dv,
+                                                                   const uint32_t adv_blocks, const uint32_t* __restrict__ hint_in,
+                                                                   uint32_t* __restrict__ hint_out) {
   __shared__ deep_sea_fam::shared s_map[BSX_BLOCK / BSX_WAVE];           // one copy per wave: in-order LDS, no s_barrier
+  if (hint_out != nullptr) {                                             // uniform: the hinted step (bsx_deep_sea_step_hinted)
+    __shared__ unsigned int s_cnt[2];
+    const bsx_pipe_role r = bsx_pipe_role_of(blockIdx.x, gridDim.x, adv_blocks, 0u);   // uniform per workgroup
+    if (r.adv) deep_sea_hint_advance(a, r.index, hint_out, s_map[0], s_cnt);
+    else deep_sea_hint_stream<K>(a.out.observation, hint_in, a.action, a.ctl.n_lanes, cells, cells_magic, dv, r.index);
+    return;
+  }
   const int wl = (int)(threadIdx.x & 63u);
   deep_sea_fam::shared& map = s_map[threadIdx.x >> 6];
   const int64_t n_lanes = a.ctl.n_lanes;
@@ -142,6 +162,101 @@ __global__ void __launch_bounds__(BSX_BLOCK) deep_sea_step1_kernel(const deep_se
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// ONE launch per step at LARGE batches (bsx_deep_sea_step_hinted; the hint mode of deep_sea_step1_kernel), with
+// bsx_pipelined_kernel's wait-free shape: the
+// first adv_blocks workgroups advance the lanes (bsx_pipe_role_of, place 0), the rest are the observation store stream,
+// and nothing in the launch depends on anything else in it.  Deterministic deep_sea has two outcomes per lane and call
+// — which one is `action == mapping[row, col]` — so the lane advance of the PREVIOUS call has left both hot cells of
+// this call's board in the lane's hint word (deep_sea_hint.h); a chunk of the stream loads hint_in[lane] and
+// action[lane] where bsx_hot_stream_body loads state[lane], and selects.  It reads no byte this launch writes: the
+// advance workgroups write `state`, the TimeStep columns and hint_out, the other half of the hint ping-pong pair.
+// Against deep_sea_step1_kernel: no transition, no LDS and no tag test in the stream, whose body stays that of
+// bsx_hot_stream_kernel<deep_sea_hot, 4, 256> plus one coalesced 4-byte load per chunk.
+// With no stream workgroups the same launch is the PRIMING advance (no valid hint_in yet): it leaves hint_out and is followed
+// by the unchanged store stream over the state column.
+//
+// The advance workgroups: the lean two-lanes-per-thread body of bsx_advance2_kernel (bsx_advance_body<Fam, true, -1, 2>:
+// the same loads, state store, TimeStep stores and counter flush; the transition with the draws compiled out, as in
+// deep_sea_step1_kernel) + the hint of the NEW word, one more look-up in the LDS copy of the mapping per lane.
+__device__ __forceinline__ void deep_sea_hint_advance(const deep_sea_fam::args& a, uint32_t block_id, uint32_t* __restrict__ hint_out,
+                                                      deep_sea_fam::shared& s_fam, unsigned int* s_cnt) {
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  deep_sea_fam::stage(a, s_fam);
+  __syncthreads();
+  const uint64_t step = bsx_step_of(a.ctl);
+  int64_t i[2];
+  bool mine[2];
+  int act[2], type[2] = {-1, -1};
+  int32_t st[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    i[h] = (int64_t)block_id * (2 * BSX_BLOCK) + h * BSX_BLOCK + threadIdx.x;
+    mine[h] = i[h] < a.ctl.n_lanes;
+    act[h] = 0; st[h] = 0;
+    if (mine[h]) {
+      act[h] = a.action[i[h]];                              // (no ring, no forced reset: the launcher's conditions)
+      st[h] = a.state[i[h]];
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (mine[h]) {
+      const uint64_t lane = a.ctl.lane_offset + (uint64_t)i[h];
+      int32_t nst; double reward;
+      type[h] = deep_sea_fam::advance<true, 1>(a, s_fam, i[h], lane, step, st[h], act[h], nst, reward);
+      a.state[i[h]] = nst;
+      hint_out[i[h]] = ds_hint_pack(nst & 0xFF, (nst >> 8) & 0xFF, nst & DS_RESET_BIT, a.size, s_fam.map);
+      bsx_emit_at<0, 0, false>(a.ctl, a.out, i[h], i[h], lane, step, type[h], reward);
+    }
+    bsx_count_types(a.ctl, type[h], s_cnt);
+  }
+  bsx_final_barrier();
+  bsx_flush_counts(a.ctl, s_cnt, block_id);
+}
+
+// The stream workgroups: bsx_hot_stream_body<deep_sea_hot, K, BSX_BLOCK> for rows of a multiple of 4 floats (a chunk never
+// straddles two lanes, the array has no ragged tail) — the same chunk -> address map, guards and plain 16-byte stores.
+template <int K>
+__device__ __forceinline__ void deep_sea_hint_stream(float* __restrict__ obs, const uint32_t* __restrict__ hint_in,
+                                                     const int32_t* __restrict__ action, int64_t n_lanes, uint32_t cells,
+                                                     uint32_t cells_magic, bsx_div64 dv, uint32_t block_id) {
+  const uint64_t total = (uint64_t)n_lanes * cells;                      // floats in the array
+  const uint64_t F0 = (uint64_t)block_id * (uint64_t)(K * 4 * BSX_BLOCK);
+  const uint64_t lane_b = __umul64hi(F0, dv.m) >> dv.s;                  // uniform
+  const uint32_t r_b = (uint32_t)(F0 - lane_b * cells);                  // < cells
+  bsx_f4* __restrict__ o4 = reinterpret_cast<bsx_f4*>(obs + F0);
+  const uint32_t* __restrict__ hi = hint_in + lane_b;
+  const int32_t* __restrict__ ac = action + lane_b;
+
+  int r0[K];
+  uint32_t h0[K];
+  int32_t a0[K];
+  bool live[K];
+#pragma unroll
+  for (int u = 0; u < K; ++u) {
+    const uint32_t c = (threadIdx.x >> 6) * (K * 64) + u * 64 + (threadIdx.x & 63);   // each wave owns K consecutive KiB
+    const uint32_t f = r_b + (c << 2);                                   // float offset from lane_b's row start
+    const uint32_t dl = __umulhi(f, cells_magic);
+    r0[u] = (int)(f - dl * cells);
+    live[u] = F0 + ((uint64_t)c << 2) + 3 < total;                       // (then lane_b + dl < n_lanes: cells % 4 == 0)
+    h0[u] = live[u] ? hi[dl] : 0u;
+    a0[u] = live[u] ? ac[dl] : 0;
+  }
+#pragma unroll
+  for (int u = 0; u < K; ++u) {
+    if (!live[u]) continue;
+    const int hot = ds_hint_hot(h0[u], a0[u]);
+    const int p0 = hot < 0 ? -1 : hot - r0[u];
+    bsx_f4 v;
+    v.x = p0 == 0 ? 1.0f : 0.0f;
+    v.y = p0 == 1 ? 1.0f : 0.0f;
+    v.z = p0 == 2 ? 1.0f : 0.0f;
+    v.w = p0 == 3 ? 1.0f : 0.0f;
+    o4[(threadIdx.x >> 6) * (K * 64) + u * 64 + (threadIdx.x & 63)] = v;
+  }
+}
+
 // The cfg's range check, the same for every entry point.
 static int deep_sea_check_cfg(const bsx_deep_sea_t* cfg) {
   return (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) ? BSX_ERANGE : 0;
@@ -195,10 +310,39 @@ extern "C" int bsx_deep_sea_step(const bsx_deep_sea_t* cfg, const bsx_call_t* ca
     const uint64_t blocks = (total + (uint64_t)K * 4 * BSX_BLOCK - 1) / ((uint64_t)K * 4 * BSX_BLOCK);
     if (blocks > 0x7FFFFFFFull) return BSX_EINVAL;
     deep_sea_step1_kernel<K><<<dim3((unsigned)blocks), dim3(BSX_BLOCK), 0, (hipStream_t)call->hip_stream>>>(
-        a, cells, bsx_div_magic(cells), bsx_make_div64(cells));
+        a, cells, bsx_div_magic(cells), bsx_make_div64(cells), 0u, nullptr, nullptr);
     return bsx_launch_status();
   }
   return bsx_pair_call<deep_sea_fam, deep_sea_hot, 4>(a, call, action, state, out, cells, deep_sea_hot{cfg->size});
+}
+
+extern "C" int bsx_deep_sea_step_hinted(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
+                                        bsx_timestep_t out, double* info, const uint32_t* const hint_in, uint32_t* const hint_out) {
+  if (cfg == nullptr || call == nullptr) return BSX_ENULL;
+  // (the 16-byte alignment of the boards is one of this entry's modes: BSX_EMODE, ahead of the common checks' BSX_EALIGN)
+  if ((reinterpret_cast<uintptr_t>(out.observation) & 15u) != 0) return BSX_EMODE;
+  deep_sea_fam::args a;
+  int rc = deep_sea_make(cfg, call, action, state, out, info, &a);
+  if (rc != 0) return rc;
+  const uint32_t cells = (uint32_t)(cfg->size * cfg->size);
+  if (!cfg->deterministic || !bsx_ctl_lean(a.ctl) || bsx_call_obs(call) != 0 || bsx_call_index(call) || call->obs_paint != nullptr ||
+      call->n_steps > 1 || call->action_ring > 1 || call->force_reset != 0 || !(call->flags & BSX_CALL_STATE_TAGGED) || (cells & 3u) != 0)
+    return BSX_EMODE;
+  if (call->n_lanes == 0) return 0;
+  if (hint_out == nullptr || hint_out == hint_in) return BSX_ENULL;
+  hipStream_t st = (hipStream_t)call->hip_stream;
+  const uint64_t adv_blocks = (uint64_t)((bsx_blocks_of(call->n_lanes) + 1) / 2);          // two lanes per thread
+  const uint64_t str_blocks = hint_in == nullptr ? 0 : bsx_flat_blocks((uint64_t)call->n_lanes * cells, PAIR_DEEP_SEA_K);
+  if (adv_blocks + str_blocks > 0x7FFFFFFFull) return BSX_EINVAL;
+  const uint32_t magic = bsx_div_magic(cells);
+  deep_sea_step1_kernel<PAIR_DEEP_SEA_K><<<dim3((unsigned)(adv_blocks + str_blocks)), dim3(BSX_BLOCK), 0, st>>>(
+      a, cells, magic, bsx_make_div64(cells), (uint32_t)adv_blocks, hint_in, hint_out);
+  // priming: no hint of this call exists yet — the boards come from the state column the advance has just written
+  if (hint_in == nullptr) {
+    rc = bsx_launch_hot_stream<deep_sea_hot, PAIR_DEEP_SEA_K>(out.observation, state, call->n_lanes, cells, magic, deep_sea_hot{cfg->size}, st);
+    if (rc != 0) return rc;
+  }
+  return bsx_launch_status();
 }
 
 extern "C" int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,

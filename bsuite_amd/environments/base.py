@@ -111,6 +111,18 @@ class Environment(dm_env.EnvironmentBase):
   # one launch needs for advance AND stores once other workgroups' stores hide behind it.  Kept as an option (tests,
   # A/B: bench.py --row-path on).
   row_path_min_bytes = None
+  # deep_sea: a step() whose observations are MORE than this many bytes goes through bsx_deep_sea_step_hinted where the call
+  # is eligible (DeepSea._hint_static_ok, and per call `_call`): ONE launch — lane advance and observation stream side by
+  # side, the stream reading the hint column the previous call's advance left (csrc/deep_sea_hint.h) — instead of lane
+  # advance + stream.  None = never (every other family).  Read once, at the first step, like row_path_min_bytes: a test
+  # sets it to 0 on an instance.  `_hint_valid`: the hint column `_hint[_hint_cur]` describes the state column as it is
+  # now — set by a hinted call, cleared by everything else that moves the state or the call index (reset(), mark_reset(),
+  # load_state_dict(), every multi-step call, a wrapper or Logging being installed, a graph capture); the next eligible call
+  # then primes (two launches).  An environment recorded into a grouped launch leaves the path for good.  The columns
+  # are scratch: allocated on first use, never part of a state_dict().  (A captured graph REPLAYED between eager steps moves
+  # the state column without this object seeing it: call reset() / mark_reset() / load_state_dict() — or anything else in
+  # the list above — before stepping eagerly again, or keep hint_min_bytes = None on such an instance.)
+  hint_min_bytes = None
   # Families with a single-launch step (deep_sea): the bit of the packed state word that carries the parity of the
   # call index that reads the word next, and all the bits of the word that are the library's bookkeeping (never part of a
   # state_dict).  The flag BSX_CALL_STATE_TAGGED is only set where every call index is exactly the previous one plus 1 —
@@ -182,6 +194,12 @@ class Environment(dm_env.EnvironmentBase):
     self._linear_eval_out = None       # evaluate_linear() / evaluate_mlp(): the three [B] columns and the final observation rows
     self._state_alt = None             # pipelined rollouts: the scratch state column (allocated on first use)
     self._row_buf = None               # the row scratch of _row_scratch() (allocated on first use)
+    self._hint_ok = False              # hint_min_bytes: the static half of the rule, decided at the first step
+    self._hint_valid = False
+    self._hint = None                  # the ping-pong pair of hint columns (allocated on first use)
+    self._hint_cur = 0
+    self._hint_argv = None
+    self.hint_launches = [0, 0, 0]     # calls of an environment on the hinted path: one launch / priming / any other path
     self._dev_index = self._device.index
     self._step_index = 0
     self._buf = 0
@@ -347,6 +365,7 @@ class Environment(dm_env.EnvironmentBase):
     call = self._call_desc
     call.force_reset, call.n_steps = 0, 0
     self._sync_wrap()
+    self._hint_ok = False                      # (a prepared group steps the state column without this object: hint_min_bytes)
     call.stream.step_index = 0
     call.action_ring = ring
     self._buf = 1 % self._num_buffers
@@ -498,7 +517,32 @@ class Environment(dm_env.EnvironmentBase):
       self._call_desc.flags = _native.CALL_STATE_TAGGED if self._tag_calls else 0
     self._call_desc.flags |= self._obs_flags
     self._tag_host_count = self._tag_calls and not self._device_step_counter
+    self._hint_ok = (self.hint_min_bytes is not None and self._tag_calls and self._hint_static_ok()
+                     and B * int(np.prod(self._obs_shape)) * 4 > self.hint_min_bytes)
     self._allocated = True
+
+  def _hint_static_ok(self) -> bool:
+    """Subclass hook (hint_min_bytes): is this environment, as constructed, one whose eager steps may go through the
+    family's hinted entry point?"""
+    return False
+
+  def _hinted_call(self, b: int, action_ptr: int):
+    """(entry point, arguments) of a step() on the hinted path: the previous call's hint column if it is valid, else NULL —
+    a priming call — and the other column to write."""
+    if self._hint is None:
+      self._hint = torch.empty((2, self._batch), dtype=torch.int32, device=self._device)
+      self._hint_fn = getattr(_native.lib, f'bsx_{self._abi_name}_step_hinted')
+      self._hint_ptrs = (self._hint[0].data_ptr(), self._hint[1].data_ptr())
+      self._hint_argv = [a + [None, None] for a in self._argv]
+    argv = self._hint_argv[b]
+    argv[2] = action_ptr
+    cur = self._hint_cur
+    argv[-2] = self._hint_ptrs[cur] if self._hint_valid else None
+    argv[-1] = self._hint_ptrs[1 - cur]
+    self.hint_launches[0 if self._hint_valid else 1] += 1
+    self._hint_cur = 1 - cur
+    self._hint_valid = False           # (until the call has been made: _call)
+    return self._hint_fn, argv
 
   def _new_outputs(self, lead, place, observation=None):
     """One set of output buffers: reward / discount f32 and step_type int8 of shape `lead` ((B,), or (T, B) for a
@@ -519,6 +563,7 @@ class Environment(dm_env.EnvironmentBase):
     w = self._call_desc.wrap
     w.kind, w.param, w.seed, w.param2 = self._wrap
     self._wrap_applied = self._wrap
+    self._hint_valid = False
 
   def _redirected(self, method, *args):
     """Kernels launch in the current device's context: a launching method of an environment that lives elsewhere
@@ -548,26 +593,38 @@ class Environment(dm_env.EnvironmentBase):
       w = self._call_wrap
       w.kind, w.param, w.seed, w.param2 = self._wrap
       self._wrap_applied = self._wrap
+      self._hint_valid = False
     hip_stream = _current_raw_stream(self._dev_index)
     call.hip_stream = hip_stream
-    argv = self._argv[b]
+    fn, argv = self._fn, self._argv[b]
     argv[2] = action_ptr
+    hinted = False
+    if self._hint_ok:                              # (hint_min_bytes: deep_sea at large batches)
+      # what bsx_deep_sea_step_hinted refuses, and a capture: a replay would read the hints of the capture over and over
+      if (force_reset or self._logging is not None or self._wrap[0] >= _native.WRAP_NOISE or self._grouped_by is not None
+          or call.action_ring > 1 or torch.cuda.is_current_stream_capturing()):
+        self._hint_valid = False
+        self.hint_launches[2] += 1
+      else:
+        fn, argv = self._hinted_call(b, action_ptr)
+        hinted = True
     if self._device_step_counter:
       if self._deferred_steps is not None:
         # inside `step_counter_deferred()`: call index = device counter + position in the block
         self._call_stream.step_index = self._deferred_steps
-        rc = self._fn(*argv)
+        rc = fn(*argv)
         self._call_stream.step_index = 0
         self._deferred_steps += 1
       else:
-        rc = self._fn(*argv)
+        rc = fn(*argv)
         if rc == 0 and self._shared_step_counter is None:
           rc = _native.lib.bsx_counter_add(self._step_base.data_ptr(), 1, hip_stream)
     else:
       self._call_stream.step_index = self._step_index
-      rc = self._fn(*argv)
+      rc = fn(*argv)
     if rc != 0:
       _native.check(rc, f'{type(self).__name__} step')
+    self._hint_valid = hinted
     self._step_index += 1
     return b
 
@@ -579,7 +636,7 @@ class Environment(dm_env.EnvironmentBase):
       return self._redirected(self._launch_steps, fn, args, T, what)
     call = self._call_desc
     call.force_reset, call.n_steps = 0, T
-    self._sync_wrap()
+    self._sync_wrap()                   # (clears _hint_valid: these calls move the state column and the call index)
     hip_stream = _current_raw_stream(self._dev_index)
     call.hip_stream = hip_stream
     # the call index of the first step: the host count, or 0 beside the device counter, which is then moved on by T
@@ -619,6 +676,7 @@ class Environment(dm_env.EnvironmentBase):
       # state column, pending-miss bits of catch included — and the kernels they launch were chosen without Logging)
       raise RuntimeError('enable_logging() on a segment of prepared sweep groups: SweepBatch.release_groups() first')
     self._ensure_allocated()
+    self._hint_valid = False
     if self._logging is None:
       # Families that fold an info column only at episode ends (cartpole, mountain_car) switch to the
       # reference's per-step accumulation under Logging, whose rows snapshot the columns mid-episode:
@@ -755,6 +813,7 @@ class Environment(dm_env.EnvironmentBase):
   def _mark_reset(self, mask):
     if _current_device() != self._dev_index:
       return self._redirected(self._mark_reset, mask)
+    self._hint_valid = False
     col = self._info_pending_column
     # `folded`: the info columns are maintained per episode (no Logging) — where _info_columns() decides it
     folded = 1 if (self._logging is None and col is not None) else 0
@@ -1776,6 +1835,7 @@ class Environment(dm_env.EnvironmentBase):
   def load_state_dict(self, d: Dict[str, Any]):
     self._ensure_allocated()
     self._scalar_last_type = None       # (scalar view: no action check until the next TimeStep says where the episode is)
+    self._hint_valid = False
     for k, v in self._state.items():
       v.copy_(d[k])
     self._info.copy_(d['__info'])

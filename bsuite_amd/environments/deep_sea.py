@@ -79,6 +79,16 @@ class DeepSea(base.Environment):
   _state_tag_bit = 1 << 18
   _state_lib_bits = 1 << 18
 
+  # Above 1 GiB of boards per step — where deep_sea_step1_kernel's reach ends — the eager step of a deterministic batch is
+  # ONE launch again (bsx_deep_sea_step_hinted; base.Environment.hint_min_bytes has the rule and what invalidates a hint).
+  hint_min_bytes = 1 << 30
+
+  def _hint_static_ok(self) -> bool:
+    # what bsx_deep_sea_step_hinted refuses for good: draws per step, chunks that straddle lanes, anything but dense
+    # float32 boards, the MT19937-exact generators, the scalar view's f64 reward
+    return (bool(self._deterministic) and (self._size * self._size) % 4 == 0 and not self._scalar and not self._delta
+            and not self._index and not self._obs_flags and self._rng_mode == 'philox')
+
   _policy_abi = 'bsx_deep_sea_policy_rollout'
   _policy_eval_abi = 'bsx_deep_sea_policy_evaluate'
   _policy_sample_abi = 'bsx_deep_sea_policy_sample'

@@ -273,6 +273,21 @@ typedef struct {
 int bsx_deep_sea_step(const bsx_deep_sea_t* cfg /*host*/, const bsx_call_t* call /*host*/,
                       const int32_t* action, int32_t* state, bsx_timestep_t out, double* info);
 
+/* The eager step of a LARGE deterministic batch in ONE launch (v12, additive).  bsx_deep_sea_step's arguments plus the two
+ * halves of a ping-pong pair of hint columns, uint32 [B] each (csrc/deep_sea_hint.h): every call's lane advance leaves in
+ * hint_out[i] the hot cells of both boards lane i can show after its NEXT call, and the observation stream of a call reads
+ * hint_in — the hint_out of the call before — and the action column instead of the state column, so the two halves of the step
+ * share a launch without either waiting for the other.  The caller passes the previous call's hint_out as hint_in, and
+ * hint_in = NULL whenever that column does not describe `state` as it is now — the first call, or after anything else has
+ * written `state` (another entry point, a reset mark, a restored column): that call is two launches and primes hint_out.
+ * Outputs, state, info and counters are bsx_deep_sea_step's, bit for bit.
+ * BSX_EMODE, before any device work, for anything but: deterministic cfg, no Logging / RewardNoise / MT19937-exact draws /
+ * reward_f64, float32 boards (no observation code, no index mode, no obs_paint), n_steps <= 1, action_ring <= 1,
+ * force_reset == 0, BSX_CALL_STATE_TAGGED set (the call indices are consecutive), size * size a multiple of 4, and
+ * out.observation on a 16-byte boundary.  hint_out NULL or equal to hint_in: BSX_ENULL. */
+int bsx_deep_sea_step_hinted(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
+                             bsx_timestep_t out, double* info, const uint32_t* hint_in, uint32_t* hint_out);
+
 /* ---- catch : bsuite/environments/catch.py:45-117 ------------------------------------------ */
 typedef struct {
   int32_t rows;     /* catch.py:46 (default 10); 2..64 */

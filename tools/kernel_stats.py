@@ -17,7 +17,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OURS = ('bsx_', 'small_obs', 'sweep_', 'pair_mixed', 'mnist_')
+OURS = ('bsx_', 'small_obs', 'sweep_', 'pair_mixed', 'mnist_', 'deep_sea_')
 
 
 def main():
