@@ -1,6 +1,6 @@
-"""What the GPU edge-grid tests (tests/test_gpu_physics_edges.py, tests/test_gpu_grid_edges.py) share: snapshots of a TimeStep and
-of what an environment holds after a call, as bit patterns on the device, and their exact comparison with the lanes that
-differ named in the failure."""
+"""What the GPU edge-grid tests (tests/test_gpu_physics_edges.py, tests/test_gpu_grid_edges.py,
+tests/test_gpu_chain_edges.py) share: snapshots of a TimeStep and of what an environment holds after a call, as bit patterns
+on the device, and their exact comparison with the lanes that differ named in the failure."""
 import torch
 
 from tests import engine_util as eu

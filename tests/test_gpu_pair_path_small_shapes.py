@@ -69,12 +69,13 @@ def test_two_lanes_per_thread_advance_at_small_shapes():
 
 @pytest.mark.timeout(900)
 def test_wide_row_stream_chunk_counts():
-  """The wide-row store stream with 1 and 4 chunks per thread (tuning build; the product library has K = 2)."""
+  """The wide-row store stream with 1 and 4 chunks per thread (tuning build; the product library has K = 2): the row-path
+  parity tests, and the mixed-phase edge grid on the row path (tests/test_gpu_chain_edges.py)."""
   from bsuite_amd import build as _build
   for k in ('1', '4'):
     env = dict(os.environ, BSX_NATIVE_LIB=_build.build(tuning=True), BSX_ROW_STREAM_K=k, PYTHONPATH=ROOT)
     p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
-                        'tests/test_gpu_wide_rows.py', '-k', 'bit_exact'],
+                        'tests/test_gpu_wide_rows.py', 'tests/test_gpu_chain_edges.py', '-k', 'bit_exact or chain_edges_rows'],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=400)
     tail = p.stdout[-3000:]
     assert p.returncode == 0, tail
@@ -86,14 +87,17 @@ def test_two_lanes_per_thread_eager_step_at_small_shapes():
   """small_obs_eager2_kernel (the lean eager step of bandit / discounting_chain / memory_len / cartpole / mountain_car
   with two lanes per thread) is size-gated at 2048+ workgroups: every parity test of those families once more with
   BSX_EAGER2_MIN_BLOCKS=1 (tuning build) — one-lane and ragged batches, both variants of cartpole; and with four lanes
-  per thread, the form that was measured and not adopted."""
+  per thread, the form that was measured and not adopted.  With them the mixed-phase edge grid of memory_chain and
+  discounting_chain (tests/test_gpu_chain_edges.py; its large-batch and several-episode tests reach the kernel by size or
+  are rollouts)."""
   from bsuite_amd import build as _build
   for lpt in ('2', '4'):
     env = dict(os.environ, BSX_NATIVE_LIB=_build.build(tuning=True), BSX_EAGER2_MIN_BLOCKS='1', BSX_EAGER_LPT=lpt, PYTHONPATH=ROOT)
     p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
                         'tests/test_gpu_golden.py', 'tests/test_gpu_oracle_batch.py', 'tests/test_gpu_dm_env_conformance.py',
-                        'tests/test_gpu_engine_features.py',
-                        '-k', 'bandit or discounting or memory or cartpole or mountain_car or swingup'],
+                        'tests/test_gpu_engine_features.py', 'tests/test_gpu_chain_edges.py',
+                        '-k', '(bandit or discounting or memory or cartpole or mountain_car or swingup) and not tiled_large_batch '
+                        'and not several_episodes'],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=400)
     tail = p.stdout[-3000:]
     assert p.returncode == 0, tail
