@@ -32,7 +32,12 @@ class MNISTBandit(base.Environment):
     images = np.asarray(images)
     if images.dtype != np.int8:
       raise TypeError('images must be int8, as bsuite/utils/datasets.py:55-56 parses them')
-    labels = np.asarray(labels, np.uint8)
+    labels = np.asarray(labels)
+    # the packed state word keeps the label in four bits below the reset bit (csrc/mnist_fam.h): a label of 16 would read as
+    # "reset pending", one of 32 as "showing".  10..15 are accepted: no action of the spec equals them, as in the reference.
+    if labels.size and (labels.min() < 0 or labels.max() > 15):
+      raise ValueError('labels must be in 0..15')
+    labels = np.asarray(labels, np.uint8)          # (no copy of a uint8 array: environments on one dataset share its tables)
     num_data = len(labels)
     self._num_data = int(fraction * num_data)
     self._image_shape = tuple(images.shape[1:])

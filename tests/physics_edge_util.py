@@ -25,6 +25,12 @@ TWO_PI = 2.0 * np.pi
 CASES = [('cartpole', {}), ('cartpole_swingup', {}), ('mountain_car', {}),
          ('cartpole', dict(max_time=50.)), ('cartpole_swingup', dict(max_time=50.)), ('mountain_car', dict(max_steps=5000))]
 CASE_IDS = [f + ('_' + '_'.join(f'{k}{v}' for k, v in kw.items()) if kw else '') for f, kw in CASES]
+# the segments of the grouped test: the sweep ids whose settings (but for the seed) are these.  cartpole/0 and mountain_car/0
+# are the default-argument cases; swing-up's sweep has no id with the default thresholds (its first is upright from
+# cos(theta) > 0 on), so that segment brings a grid of its own, held to the same conditions by tests/test_physics_edges_host.py
+GROUPED_IDS = {'cartpole/0': ('cartpole', {}), 'cartpole_swingup/0': ('cartpole_swingup', dict(height_threshold=0.0, x_reward_threshold=1.0)),
+               'mountain_car/0': ('mountain_car', {})}
+GROUPED_CASES = [c for c in GROUPED_IDS.values() if c not in CASES]
 
 CARTPOLE_PREDICATES = ('adv_small', 'adv_large', 'wrap_up', 'wrap_down', 'wrap_floor', 'theta_in_at_f32_2pi', 'timeout',
                        'timeout_and_threshold', 'x_in', 'x_out')
@@ -166,15 +172,19 @@ def make_oracle(g, rows=None):
   return orc
 
 
-def oracle_step(g, rows=None):
-  """One step of the reference from the grid: (orc, (step_type, reward, discount, obs) copies)."""
+def oracle_step(g, rows=None, reset_mask=None):
+  """One step of the reference from the grid: (orc, (step_type, reward, discount, obs) copies).  reset_mask: bool [B], the
+  lanes that are called with reset() instead of step()."""
   orc = make_oracle(g, rows)
+  if reset_mask is not None:
+    orc.reset_next[np.asarray(reset_mask)] = 1
   a = g['action'] if rows is None else g['action'][np.asarray(rows)]
   return orc, tuple(v.copy() for v in orc.call(a, STEP0))
 
 
-def load(env, g, rows=None):
-  """Loads the grid into an engine environment (possibly wrapped) through state_dict() / load_state_dict()."""
+def load(env, g, rows=None, step0=STEP0):
+  """Loads the grid into an engine environment (possibly wrapped) through state_dict() / load_state_dict().  step0 = None
+  keeps the environment's own call index."""
   import torch          # pylint: disable=import-outside-toplevel
   r = eu.raw(env)
   rows = slice(None) if rows is None else np.asarray(rows)
@@ -184,7 +194,8 @@ def load(env, g, rows=None):
   d['steps'] = torch.from_numpy(np.array(g['k'][rows], np.int32)).to(dev)          # RESET_BIT clear: running episodes
   per_step = g['family'] == 'cartpole_swingup' or '__logging_steps' in d
   d['__info'] = torch.from_numpy(np.ascontiguousarray(running_info(g, per_step)[:, rows])).to(dev)
-  d['__step_index'] = STEP0
+  if step0 is not None:
+    d['__step_index'] = step0
   assert tuple(d['state'].shape) == shape and d['steps'].dtype == torch.int32
   r.load_state_dict(d)
 
@@ -220,6 +231,17 @@ def predicates(g, orc, want):
     p.update(up_true=up, up_false=~up, flag6_pos=obs[:, 6] == 1.0, flag6_neg=obs[:, 6] == -1.0,
              flag7_pos=obs[:, 7] == 1.0, flag7_neg=obs[:, 7] == -1.0)
   return p
+
+
+def segment_rows(g, n, seed):
+  """int64 [n]: the rows of the grid a grouped segment of n lanes is loaded with (the cartpole grids are larger than a
+  segment): a wave of every branch predicate, then seeded random rows."""
+  orc, want = oracle_step(g)
+  pred = predicates(g, orc, want)
+  picked = np.concatenate([np.flatnonzero(pred[name])[:MIN_LANES] for name in PREDICATES[g['family']]])
+  assert len(picked) < n
+  fill = np.random.default_rng(seed).integers(0, g['lanes'], size=n - len(picked))
+  return np.concatenate([picked, fill])
 
 
 def threshold_ties(g, orc):

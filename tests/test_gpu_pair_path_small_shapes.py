@@ -89,15 +89,16 @@ def test_two_lanes_per_thread_eager_step_at_small_shapes():
   BSX_EAGER2_MIN_BLOCKS=1 (tuning build) — one-lane and ragged batches, both variants of cartpole; and with four lanes
   per thread, the form that was measured and not adopted.  With them the mixed-phase edge grid of memory_chain and
   discounting_chain (tests/test_gpu_chain_edges.py; its large-batch and several-episode tests reach the kernel by size or
-  are rollouts)."""
+  are rollouts), and that of bandit (tests/test_gpu_bandit_edges.py; the mnist cases of that file, ids edge_mnist_*, have no
+  such kernel)."""
   from bsuite_amd import build as _build
   for lpt in ('2', '4'):
     env = dict(os.environ, BSX_NATIVE_LIB=_build.build(tuning=True), BSX_EAGER2_MIN_BLOCKS='1', BSX_EAGER_LPT=lpt, PYTHONPATH=ROOT)
     p = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-x', '-m', 'gpu', '-p', 'no:cacheprovider',
                         'tests/test_gpu_golden.py', 'tests/test_gpu_oracle_batch.py', 'tests/test_gpu_dm_env_conformance.py',
-                        'tests/test_gpu_engine_features.py', 'tests/test_gpu_chain_edges.py',
+                        'tests/test_gpu_engine_features.py', 'tests/test_gpu_chain_edges.py', 'tests/test_gpu_bandit_edges.py',
                         '-k', '(bandit or discounting or memory or cartpole or mountain_car or swingup) and not tiled_large_batch '
-                        'and not several_episodes'],
+                        'and not several_episodes and not edge_mnist and not grouped_launches_equal_standalone_envs'],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=400)
     tail = p.stdout[-3000:]
     assert p.returncode == 0, tail

@@ -11,12 +11,18 @@ made of (tests/test_physics_edges_host.py proves the grid reaches each on at lea
      load_state_dict reaches — are held to max(1e-6, 2 x the error measured on the MI355X) per family and theta_dot band,
      which is 1e-6 everywhere (MEASURED below; profiles/physics_edges/README.md has the measurement per component);
   B. every other path against the eager step from the same loaded state, T = 1 and T = 3 (a lane that ends at step 1
-     resets inside the fused loop at step 2): int32 bit patterns, no tolerance, every row.
+     resets inside the fused loop at step 2): int32 bit patterns, no tolerance, every row.  Among them the per-lane reset
+     (step(reset_mask=) / mark_reset(): unmarked lanes against the eager step, marked lanes against the reference's reset),
+     the device-resident call counter, and the grouped launches of a SweepBatch (the duo / small_mixed group kernels, the
+     sweep's phase 0, its split cut and the pipelined kernel) against stand-alone environments loaded with the same rows.
 """
 import numpy as np
 import pytest
 import torch
 
+import bsuite_amd
+from bsuite_amd import sweep
+from bsuite_amd import sweep_batch as sb
 from bsuite_amd.utils import wrappers
 from tests import edge_snap_util as es
 from tests import engine_util as eu
@@ -212,7 +218,17 @@ def _policies(family, B):
   w2 = torch.randn((3, H + 1), generator=gen).cuda().contiguous()
   obs = torch.randn((B, 1, D), generator=gen).cuda().contiguous()
   draw = dict(temperature=1.0, sample_seed=(1 << 40) + 77)
+  # the two-hidden-layer triple from a generator of its own (the draws above stay what they were).  Under seed 31 it leaves an
+  # action out in every family (cartpole 2 %, swing-up 0.1 %, mountain_car 5 %); 884 was chosen on the CPU with the host
+  # restatement of tests/test_mlp2_host.py (_restate) over seeds 1..1499: every action on at least 8 % of the rows, every family
+  gen2 = torch.Generator(device='cpu')
+  gen2.manual_seed(884)
+  H1, H2 = 5, 4
+  v1 = torch.randn((H1, D + 1), generator=gen2).cuda().contiguous()
+  v2 = torch.randn((H2, H1 + 1), generator=gen2).cuda().contiguous()
+  v3 = torch.randn((3, H2 + 1), generator=gen2).cuda().contiguous()
   return obs, [('rollout_linear', 'evaluate_linear', (w,), {}), ('rollout_mlp', 'evaluate_mlp', (w1, w2), {}),
+               ('rollout_mlp2', 'evaluate_mlp2', (v1, v2, v3), {}),
                ('sample_linear', 'evaluate_sampled_linear', (w,), draw), ('sample_mlp', 'evaluate_sampled_mlp', (w1, w2), draw)]
 
 
@@ -266,3 +282,143 @@ def test_two_lanes_per_thread_step_equals_the_small_batch(family, kwargs):
   after = _snap_after(env)
   _assert_after(after, e['after'][0], (family, 'two lanes per thread'), rows=rows_t)
   assert after['counters'].tolist() == [int((e['ts'][0]['step_type'][rows_t] == 2).sum()), 0]
+
+
+# ------------------------------------------------------------------------------------- per-lane resets, the device counter
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('family,kwargs', CASE_PARAMS)
+def test_reset_mask_and_mark_reset_on_the_grid(family, kwargs):
+  """A seeded third of the lanes is marked — lanes about to time out, to cross a threshold, at the wall among them.  The
+  marked lanes give FIRST with the oracle's reset observation (PhysicsChecker as it stands: a marked lane has no threshold
+  to tie on) and the info columns of the reference called with reset(); the unmarked lanes equal the eager run bit for bit,
+  every one of them.  mark_reset() followed by the plain step is the same call."""
+  g, e = pu.grid(family, kwargs), eager(family, kwargs)
+  B = g['lanes']
+  mask = np.random.default_rng(41).random(B) < 1.0 / 3.0
+  mask_t, acts = torch.from_numpy(mask).cuda(), e['actions'][0]
+  orc, want = pu.oracle_step(g, reset_mask=mask)
+  assert (want[0][mask] == 0).all() and (want[0][~mask] != 0).all()
+  pred = pu.predicates(g, *pu.oracle_step(g))
+  for name in pu.PREDICATES[family]:
+    assert (pred[name] & ~mask).sum() >= pu.MIN_LANES // 2 and (pred[name] & mask).sum() >= 8, name      # (held on the CPU, too)
+  env = _make(family, kwargs, B)
+  pu.load(env, g)
+  ts = _snap_ts(env.step(acts, reset_mask=mask_t))
+  after = _snap_after(env)
+  # unmarked lanes: the eager step, bit for bit
+  keep = ~mask_t
+  want_ts, want_after = e['ts'][0], e['after'][0]
+  for f in es.TS_FIELDS:
+    assert torch.equal(ts[f][keep], want_ts[f][keep]), (family, 'reset_mask', f, 'unmarked lanes')
+  for k, w in want_after['state'].items():
+    assert torch.equal(after['state'][k][..., keep], w[..., keep]), (family, 'reset_mask', k, 'unmarked lanes')
+  for k, w in want_after['info'].items():
+    assert torch.equal(after['info'][k][keep], w[keep]), (family, 'reset_mask', k, 'unmarked lanes')
+  # marked lanes: FIRST, reward 0, discount 1, the reference's reset observation within the contract
+  got = (ts['step_type'].cpu().numpy(), ts['reward'].view(torch.float32).cpu().numpy(), ts['discount'].view(torch.float32).cpu().numpy(),
+         ts['observation'].view(torch.float32).cpu().numpy().reshape(B, -1))
+  assert (got[0][mask] == 0).all() and (got[1][mask] == 0).all() and (got[2][mask] == 1).all()
+  n = int(mask.sum())
+  state = {k: v[mask] for k, v in eu.oracle_physics_state(orc, family).items()}
+  chk = eu.PhysicsChecker(family, g['kwargs'], n)
+  chk.check(tuple(v[mask] for v in got), (want[0][mask], want[1][mask], want[2][mask], want[3].reshape(B, -1)[mask]), state,
+            msg=f'{family} marked lanes')
+  assert chk.max_err['observation'] <= eu.PHYS_TOL and not chk.tainted.any()
+  for k, v in orc.bsuite_info().items():      # an abandoned episode keeps what it has earned and ends nothing
+    np.testing.assert_array_equal(after['info'][k].view(torch.float64).cpu().numpy()[mask], v[mask], err_msg=f'{k} marked lanes')
+  last = int((want_ts['step_type'][keep] == 2).sum())
+  assert after['counters'].tolist() == [last, n] and after['step_index'] == pu.STEP0 + 1
+  # mark_reset(), then the plain step: the same words, the same TimeStep
+  env2 = _make(family, kwargs, B)
+  pu.load(env2, g)
+  loaded = env2._state['steps'].clone()                                         # pylint: disable=protected-access
+  env2.mark_reset(mask_t.to(torch.uint8))
+  assert torch.equal(env2._state['steps'], torch.where(mask_t, loaded | pu.RESET_BIT, loaded))      # pylint: disable=protected-access
+  _assert_ts(_snap_ts(env2.step(acts)), ts, (family, 'mark_reset'))
+  _assert_after(_snap_after(env2), after, (family, 'mark_reset'))
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('family,kwargs', CASE_PARAMS)
+def test_device_step_counter_paths_equal_the_eager_step(family, kwargs):
+  g, e = pu.grid(family, kwargs), eager(family, kwargs)
+  for path in ('step', 'rollout'):
+    what = (family, 'device_step_counter', path)
+    env = _make(family, kwargs, g['lanes'], device_step_counter=True)
+    pu.load(env, g)
+    if path == 'step':
+      got = _stack([_snap_ts(env.step(e['actions'][t])) for t in range(T_MAX)], T_MAX)
+    else:
+      got = _snap_ts(env.rollout(e['actions'][:T_MAX].contiguous()))
+    _assert_ts(got, _stack(e['ts'], T_MAX), what)
+    assert eu.raw(env).device_step_index() == pu.STEP0 + T_MAX, what
+    after = _snap_after(env)
+    after['step_index'] = eu.raw(env).device_step_index()                       # (the device counter is the authority here)
+    _assert_after(after, e['after'][T_MAX - 1], what)
+
+
+# ------------------------------------------------------------------------------------- grouped launches
+GROUPED_MODES = ['per_family', 'per_family_streams', 'small_mixed', 'small_mixed_streams', 'whole_sweep', 'whole_sweep_streams',
+                 'whole_sweep_rows_in_stream', 'whole_sweep_split', 'whole_sweep_pipelined']
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('mode', GROUPED_MODES, ids=['grouped_' + m for m in GROUPED_MODES])
+def test_grouped_launches_equal_standalone_envs(mode):
+  """A SweepBatch of cartpole/0, cartpole_swingup/0 and mountain_car/0 with grid rows loaded into their segment environments
+  before prepare_groups (each segment's own state_dict(), so its call index is kept), and catch/0 from its fresh reset so that
+  the whole-sweep group has a store stream: three grouped steps against stand-alone environments loaded with the same rows,
+  bit for bit on every row — the same kernels' cores, the same draws, identical even for f32 physics."""
+  ids, reps = list(pu.GROUPED_IDS) + ['catch/0'], 3
+  for bid, (family, kwargs) in pu.GROUPED_IDS.items():
+    assert {k: v for k, v in sweep.SETTINGS[bid].items() if k != 'seed'} == kwargs, bid
+  assert [c for c in pu.GROUPED_IDS.values() if c in pu.CASES] == [pu.CASES[0], pu.CASES[2]]      # the default-argument cases
+  grids = [pu.grid(*c) for c in pu.GROUPED_IDS.values()]
+  lanes = 16 * pu.BLOCK + 1
+  batch = sb.SweepBatch(ids, len(ids) * lanes, seed=pu.SEED)
+  acts, refs = [], []
+  for k, ((bid, begin, n), env, g) in enumerate(zip(batch.segments, batch.envs, grids + [None])):
+    assert n == lanes
+    ref = bsuite_amd.load_from_id(bid, batch=n, lane_offset=begin, num_buffers=1, seed=pu.SEED)
+    if g is None:                                  # catch/0: from its fresh reset
+      acts.append(torch.ones(n, dtype=torch.int32, device='cuda'))
+    else:
+      # (the cartpole grids are larger than a segment: a wave of every branch predicate, then seeded random rows)
+      rows = pu.segment_rows(g, n, 50 + k)
+      pred = pu.predicates(g, *pu.oracle_step(g))
+      for name in pu.PREDICATES[g['family']]:
+        assert pred[name][rows].sum() >= pu.MIN_LANES, (bid, name)
+      pu.load(env, g, rows, step0=None)
+      pu.load(ref, g, rows, step0=None)
+      acts.append(torch.from_numpy(np.array(g['action'][rows])).cuda())
+    refs.append(ref)
+  base_mode = mode.replace('_streams', '')
+  whole = base_mode.startswith('whole_sweep')
+  pipelined = base_mode == 'whole_sweep_pipelined'
+  extra = dict(rows_in_stream=base_mode == 'whole_sweep_rows_in_stream', split=base_mode == 'whole_sweep_split') if whole else {}
+  batch.prepare_groups(acts, mix_all=whole, mix_pairs=False, mix_small=base_mode == 'small_mixed', pipelined=pipelined, **extra)
+  for s in range(reps):
+    if mode.endswith('_streams'):
+      outs = batch.step_grouped_streams()
+      batch.join_streams()
+    else:
+      outs = batch.step_grouped()
+    torch.cuda.synchronize()
+    for bid, out, ref, a in zip(ids, outs, refs, acts):
+      _assert_ts(_snap_ts(out), _snap_ts(ref.step(a)), (mode, bid, s))
+  if base_mode == 'whole_sweep_split':
+    assert batch._split, 'the split cut fell back to the ordinary one'          # pylint: disable=protected-access
+  batch.sync()
+  if pipelined:
+    for ref, a in zip(refs, acts):
+      ref.step(a)
+  batch.release_groups()                         # (the lanes come back in the environments' own state columns)
+  for bid, env, ref in zip(ids, batch.envs, refs):
+    for k, v in ref.bsuite_info().items():
+      assert torch.equal(_bits(env.bsuite_info()[k]), _bits(v)), (mode, bid, k)
+    assert torch.equal(eu.raw(env).episode_counters(), eu.raw(ref).episode_counters()), (mode, bid)
+    assert torch.equal(eu.raw(env).invalid_action_count(), eu.raw(ref).invalid_action_count()), (mode, bid)
+    mine, theirs = eu.raw(env).state_dict(), eu.raw(ref).state_dict()
+    for k in eu.raw(ref)._state:                                                # pylint: disable=protected-access
+      assert torch.equal(mine[k], theirs[k]), (mode, bid, k)
+    assert torch.equal(_bits(eu.raw(env)._info), _bits(eu.raw(ref)._info)), (mode, bid, 'info columns')      # pylint: disable=protected-access

@@ -25,7 +25,8 @@ def test_grid_values_are_float32_and_the_lane_count_is_ragged(family, kwargs):
     assert (g['max_steps'] + 1) * 4 > 16384 if kwargs else (g['max_steps'] + 1) * 4 <= 16384
 
 
-@pytest.mark.parametrize('family,kwargs', pu.CASES, ids=pu.CASE_IDS)
+# (a grouped segment that is no case of its own is held to the same conditions)
+@pytest.mark.parametrize('family,kwargs', pu.CASES + pu.GROUPED_CASES, ids=pu.CASE_IDS + ['grouped_' + c[0] for c in pu.GROUPED_CASES])
 def test_every_branch_is_reached_and_few_lanes_tie(family, kwargs):
   g = pu.grid(family, kwargs)
   orc, want = pu.oracle_step(g)
@@ -39,6 +40,12 @@ def test_every_branch_is_reached_and_few_lanes_tie(family, kwargs):
     print(f'{family} {kwargs} {name}: {n} lanes, {int(pred[name][mt_rows].sum())} among the mt19937 rows')
     assert n >= pu.MIN_LANES, (name, n)
     assert int(pred[name][mt_rows].sum()) >= pu.MIN_LANES, (name, 'rows of the mt19937 environment')
+  # both sides of the seeded reset mask of the GPU file's test_reset_mask_and_mark_reset_on_the_grid
+  mask = np.random.default_rng(41).random(g['lanes']) < 1.0 / 3.0
+  for name in pu.PREDICATES[family]:
+    assert (pred[name] & ~mask).sum() >= pu.MIN_LANES // 2 and (pred[name] & mask).sum() >= 8, name
+  first = pu.oracle_step(g, reset_mask=mask)[1][0] == 0
+  np.testing.assert_array_equal(first, mask)                        # the reference called with reset() on exactly those lanes
   # both outcomes of LAST, and the time-out lanes end
   assert (st[pred['mc_timeout' if family == 'mountain_car' else 'timeout']] == 2).all()
   assert (st == 1).sum() >= pu.MIN_LANES and (st == 2).sum() >= pu.MIN_LANES
