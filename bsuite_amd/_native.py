@@ -151,7 +151,8 @@ class Mlp(ctypes.Structure):
 
 
 class Mlp2(ctypes.Structure):
-  """bsx_mlp2_t: the two-hidden-layer policy of bsx_<family>_mlp2_evaluate / bsx_<family>_mlp2_rollout."""
+  """bsx_mlp2_t: the two-hidden-layer policy of bsx_<family>_mlp2_evaluate / bsx_<family>_mlp2_rollout and their sampled siblings
+  bsx_<family>_mlp2_sample / bsx_<family>_mlp2_sample_evaluate (explore_seed is their sample seed)."""
   _fields_ = [('w1', ctypes.c_void_p), ('w2', ctypes.c_void_p), ('w3', ctypes.c_void_p), ('hidden1', ctypes.c_int32),
               ('hidden2', ctypes.c_int32), ('n_policies', ctypes.c_int32), ('policy_index', ctypes.c_void_p),
               ('epsilon', ctypes.c_double), ('explore_seed', ctypes.c_uint64), ('observation_in', ctypes.c_void_p)]
@@ -327,6 +328,11 @@ for _fam, _cfg in (('cartpole', CartpoleCfg), ('mountain_car', MountainCarCfg)):
                                          LinearEvalPtrs, _P], ctypes.c_int)
   _SIGS[f'bsx_{_fam}_mlp2_rollout'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), _P, _P,
                                         TimeStepPtrs, _P, _P], ctypes.c_int)
+  # sample_mlp2 / evaluate_sampled_mlp2: the signatures of *_mlp_sample / *_mlp_sample_evaluate with the triple of matrices
+  _SIGS[f'bsx_{_fam}_mlp2_sample'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), ctypes.c_double,
+                                       _P, _P, TimeStepPtrs, _P, _P], ctypes.c_int)
+  _SIGS[f'bsx_{_fam}_mlp2_sample_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2),
+                                                ctypes.c_double, _P, _P, LinearEvalPtrs, _P], ctypes.c_int)
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({
     'bsx_group_create': ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_G)], ctypes.c_int),

@@ -1,6 +1,7 @@
-// bsx_torso.h — bsx_<family>_mlp2_evaluate / bsx_<family>_mlp2_rollout (evaluate_mlp2, rollout_mlp2): the arguments of the ONE
+// bsx_torso.h — bsx_<family>_mlp2_evaluate / bsx_<family>_mlp2_rollout (evaluate_mlp2, rollout_mlp2) and
+// bsx_<family>_mlp2_sample_evaluate / bsx_<family>_mlp2_sample (evaluate_sampled_mlp2, sample_mlp2): the arguments of the ONE
 // kernel that serves cartpole, swing-up and mountain_car under a policy with two ReLU hidden layers (bsx_torso_kernel,
-// torso.hip), the body of its step loop, its launcher and the checks the four entry points share.  The closed loop of
+// torso.hip), the body of its step loop, its launcher and the checks the eight entry points share.  The closed loop of
 // bsx_mlp_returns.h (evaluate: three sums and the final row) and of bsx_trajectory.h (record: the TimeStep of every step and
 // the action taken), with bsx_mlp2.h's rule between the observation and the action.
 #ifndef BSX_TORSO_H_
@@ -8,10 +9,14 @@
 
 #include "bsx_trajectory.h"            // bsx_mlp_returns.h, bsx_linear_score.h, BSX_KERNARG, bsx_trajectory_store_row, the checks
 #include "bsx_mlp2.h"
+#include "bsx_gumbel.h"
 
-// How a lane's action comes from its logits: the greedy one (with the epsilon coin) is the only mode today; drawn actions
-// (softmax) are meant to join this kernel as another value.
+// How a lane's action comes from its logits: the greedy one (with the epsilon coin), or a draw from softmax(logits /
+// temperature) by Gumbel-max (bsx_gumbel.h; bsx_<family>_mlp2_sample / bsx_<family>_mlp2_sample_evaluate, sample_mlp2 /
+// evaluate_sampled_mlp2).  Uniform per launch; a compile-time parameter of the body (DRAWN) and of the walk (KEEP): twelve
+// bodies for each mode.
 #define BSX_TORSO_GREEDY 0
+#define BSX_TORSO_DRAWN 1
 
 // The policy side of the call, as the kernel reads it.
 struct bsx_torso_policy {
@@ -20,8 +25,8 @@ struct bsx_torso_policy {
   const float* w3;                 // [n_policies, 3, hidden2 + 1]
   const int32_t* policy_index;     // [n_lanes], or null: every lane takes triple 0 (n_policies == 1)
   const float* observation_in;     // [n_lanes, D]
-  double epsilon;
-  uint64_t explore_seed;
+  double epsilon;                  // BSX_TORSO_GREEDY; not read by BSX_TORSO_DRAWN
+  uint64_t explore_seed;           // BSX_TORSO_DRAWN: the sample seed
   int32_t n_policies, hidden1, hidden2;
   int32_t width;                   // layer-2 accumulators a lane keeps: the smallest of 16, 32, 64 that is >= hidden2
 };
@@ -29,7 +34,7 @@ struct bsx_torso_policy {
 struct bsx_torso_args {
   int32_t family;                  // BSX_FAM_CARTPOLE (classic or swing-up: fam.cartpole.cfg.swingup) or BSX_FAM_MOUNTAIN_CAR
   int32_t n_steps;
-  int32_t mode;                    // BSX_TORSO_GREEDY
+  int32_t mode;                    // BSX_TORSO_GREEDY or BSX_TORSO_DRAWN
   int32_t record;                  // 0: evaluate (writes `ev` after the loop); 1: record (writes `out`, `actions_out` per step)
   bsx_torso_policy p;
   bsx_linear_eval_t ev;
@@ -39,6 +44,8 @@ struct bsx_torso_args {
     cartpole_env::args cartpole;
     mountain_car_env::args mountain_car;
   } fam;
+  // (after everything the greedy bodies read: their kernarg offsets stay what they were)
+  double beta;                     // BSX_TORSO_DRAWN: 1 / temperature, finite and > 0 (the entry points check)
 };
 
 // A shared triple in the workgroup's dynamic LDS, staged once per launch (bsx_torso_stage), W = p.width:
@@ -128,8 +135,10 @@ struct bsx_torso_global {
 // j runs outside: hidden unit j of layer 1 is consumed where it is produced, by W layer-2 accumulators that stay in
 // registers across the walk — every index into acc[] is a compile-time constant.  Accumulators k >= H2 see zero weights and
 // are never read.  Layer 3 consumes accumulator k where its ReLU is taken: three logit accumulators.
-template <int D, int W, class Tab>
-__device__ __forceinline__ int32_t bsx_torso_action(Tab& t, const int H1, const int H2, const float* o) {
+//   KEEP   the drawn mode: the three logits (bsx_mlp2_logits' values, bit for bit) are copied to keep[]; the greedy bodies
+//          instantiate the walk without it, as it was before that mode.
+template <int D, int W, bool KEEP = false, class Tab>
+__device__ __forceinline__ int32_t bsx_torso_action(Tab& t, const int H1, const int H2, const float* o, float* keep = nullptr) {
   float acc[W];
   t.unit(H1);
 #pragma unroll
@@ -166,15 +175,20 @@ __device__ __forceinline__ int32_t bsx_torso_action(Tab& t, const int H1, const 
       bsx_mlp_accumulate(l, w3k, bsx_mlp_relu(acc[k]));
     }
   }
+  if constexpr (KEEP) {
+#pragma unroll
+    for (int a = 0; a < BSX_LINEAR_ACTIONS; ++a) keep[a] = l[a];
+  }
   return bsx_mlp_argmax(l);
 }
 
 // ... at the launch's width: a uniform switch, taken per step.
-template <int D, class Tab>
-__device__ __forceinline__ int32_t bsx_torso_action_of(Tab& t, const int W, const int H1, const int H2, const float* o) {
-  if (W == 16) return bsx_torso_action<D, 16>(t, H1, H2, o);
-  if (W == 32) return bsx_torso_action<D, 32>(t, H1, H2, o);
-  return bsx_torso_action<D, 64>(t, H1, H2, o);
+template <int D, bool KEEP = false, class Tab>
+__device__ __forceinline__ int32_t bsx_torso_action_of(Tab& t, const int W, const int H1, const int H2, const float* o,
+                                                       float* keep = nullptr) {
+  if (W == 16) return bsx_torso_action<D, 16, KEEP>(t, H1, H2, o, keep);
+  if (W == 32) return bsx_torso_action<D, 32, KEEP>(t, H1, H2, o, keep);
+  return bsx_torso_action<D, 64, KEEP>(t, H1, H2, o, keep);
 }
 
 // Stages a shared triple (bsx_torso_lds's layout) for a row length D that is uniform but not a compile-time constant here:
@@ -202,7 +216,8 @@ __device__ __forceinline__ void bsx_torso_stage(const bsx_torso_args& k, const i
   }
 }
 
-// evaluate_mlp2(T) / rollout_mlp2(T).  Around the policy this is bsx_mlp_returns_body (RECORD = false) and
+// evaluate_mlp2(T) / rollout_mlp2(T), and with DRAWN evaluate_sampled_mlp2(T) / sample_mlp2(T).
+// Around the policy this is bsx_mlp_returns_body (RECORD = false) and
 // bsx_trajectory_body (RECORD = true): state in Env::regs, the info columns in registers, Env::core on the registers, resets
 // computed in line, LAST / FIRST counted per thread and pooled once, state and info stored after the loop; per step either
 // bsx_eval_accumulate or the trajectory's stores — reward / discount from bsx_emit_values' lean instantiation, step_type, the
@@ -212,11 +227,15 @@ __device__ __forceinline__ void bsx_torso_stage(const bsx_torso_args& k, const i
 //   V       the family's variant (Env::numel_of(V) floats per row: cartpole 0 classic / 1 swing-up)
 //   SHARED  one triple for all lanes (n_policies == 1): staged in LDS by the kernel before this body and read from there
 //           every step; else the lane's own, read from global memory inside the step (lanes grouped by policy share loads).
+//   DRAWN   the action is a draw from softmax(logits * beta) by Gumbel-max over the walk's three logits (bsx_gumbel.h), as in
+//           bsx_gumbel_body: block 0 of stream BSX_STREAM_SAMPLE of (p.explore_seed, lane, step), nothing drawn and action
+//           0 on a step that resets; no epsilon coin.  A compile-time mode: the greedy bodies' instruction streams are what
+//           they were without it.
 // The arguments are read through three views (bsx_torso_view): one before the loop, one per step, one after the loop.
 // No barrier, no atomic and no LDS write inside the loop.
 // (The skeleton — prologue, coin, per-step stores, the n_first rule, epilogue — is the third copy of those two bodies': keep
 // the three alike.)
-template <class Fam, int V, bool SHARED, bool RECORD>
+template <class Fam, int V, bool SHARED, bool RECORD, bool DRAWN = false>
 __device__ __forceinline__ void bsx_torso_body(bsx_torso_kernarg ka, float* s_w, unsigned int* s_cnt) {
   typedef typename Fam::env Env;
   constexpr int D = Env::numel_of(V);
@@ -254,27 +273,42 @@ __device__ __forceinline__ void bsx_torso_body(bsx_torso_kernarg ka, float* s_w,
       const int resets = Env::reset_pending(rg) ? 1 : 0;
       const int H1 = p.hidden1, H2 = p.hidden2, W = p.width;               // 1 .. BSX_MLP_MAX_HIDDEN (the entry points check)
       int32_t best;
+      float l[BSX_LINEAR_ACTIONS];                                         // DRAWN: the walk's logits
+      (void)l;
       if constexpr (SHARED) {
         // (from an offset the compiler cannot trace to the loop's outside: bsx_mlp_returns_body; in units of 16 bytes, so
         // that the alignment of the rows stays visible)
         bsx_torso_lds<D> tab;
         tab.s = (bsx_lds_table)s_w + bsx_fresh(0u) * 4u;
         tab.W = W; tab.off3 = BSX_TORSO_W2T(H1, W); tab.off1 = tab.off3 + BSX_TORSO_W3T(H2);
-        best = bsx_torso_action_of<D>(tab, W, H1, H2, o);
+        if constexpr (DRAWN) best = bsx_torso_action_of<D, true>(tab, W, H1, H2, o, l);
+        else best = bsx_torso_action_of<D>(tab, W, H1, H2, o);
       } else {
         bsx_torso_global<D> tab;
         tab.g1 = p.w1 + (int64_t)row * BSX_MLP2_W1(D, H1);
         tab.g2 = p.w2 + (int64_t)row * BSX_MLP2_W2(H1, H2);
         tab.g3 = p.w3 + (int64_t)row * BSX_MLP2_W3(H2);
         tab.H2 = H2; tab.stride = H1 + 1; tab.k_max = H2 - 1;
-        best = bsx_torso_action_of<D>(tab, W, H1, H2, o);
+        if constexpr (DRAWN) best = bsx_torso_action_of<D, true>(tab, W, H1, H2, o, l);
+        else best = bsx_torso_action_of<D>(tab, W, H1, H2, o);
       }
-      uint32_t w0 = 0, w1 = 0, w2 = 0;
-      if (p.epsilon > 0.0 && !resets) {
-        const bsx_u32x4 u = bsx_policy_draws(p.explore_seed, lane, step);
-        w0 = u.v[0]; w1 = u.v[1]; w2 = u.v[2];
+      (void)best;
+      int act = 0;
+      if constexpr (DRAWN) {
+        // bsx_gumbel_body's decision: a lane that resets on this step takes action 0 and draws nothing.  (The action pinned
+        // where it is drawn: bsx_drawn_returns_body has the reason.)
+        if (!resets) {
+          const bsx_u32x4 u = bsx_gumbel_draws(p.explore_seed, lane, step);
+          act = (int32_t)bsx_fresh((uint32_t)bsx_gumbel_select(l, kt.beta, u.v[0], u.v[1], u.v[2]));
+        }
+      } else {
+        uint32_t w0 = 0, w1 = 0, w2 = 0;
+        if (p.epsilon > 0.0 && !resets) {
+          const bsx_u32x4 u = bsx_policy_draws(p.explore_seed, lane, step);
+          w0 = u.v[0]; w1 = u.v[1]; w2 = u.v[2];
+        }
+        act = bsx_policy_select((uint32_t)best, resets, p.epsilon, w0, w1, w2, BSX_LINEAR_ACTIONS);
       }
-      const int act = bsx_policy_select((uint32_t)best, resets, p.epsilon, w0, w1, w2, BSX_LINEAR_ACTIONS);
       double reward = 0.0;
       const int type = Env::template core<0, 0, true, false, false, V, true>(a, rg, act, i, lane, step, o, reward);
       if constexpr (!RECORD) {
@@ -329,22 +363,38 @@ static inline int bsx_check_mlp2_call(const bsx_call_t* call, const bsx_mlp2_t* 
   return bsx_check_mlp_call(call, &one, state, steps, outputs_present, info, m->w3 != nullptr ? extra : nullptr);
 }
 
+// ... and of the four sampled entry points (bsx_<family>_mlp2_sample, bsx_<family>_mlp2_sample_evaluate): the same, with the
+// rule of bsx_check_gumbel_call where the greedy calls refuse an epsilon outside [0, 1] (BSX_ERANGE: after the modes and the
+// scalars, before an empty call returns and before any pointer is looked at) — an epsilon other than 0.0 (NaN included) or an
+// inv_temperature that is not finite or not > 0.  The check is given a copy of the policy whose epsilon is 0.0 when both are
+// acceptable and out of range when either is not.
+static inline int bsx_check_mlp2_sample_call(const bsx_call_t* call, const bsx_mlp2_t* m, double inv_temperature, const float* state,
+                                             const int32_t* steps, bool outputs_present, const double* info, const void* extra) {
+  bsx_mlp2_t q = *m;
+  const bool ok = m->epsilon == 0.0 && __builtin_isfinite(inv_temperature) && inv_temperature > 0.0;
+  q.epsilon = ok ? 0.0 : 2.0;
+  return bsx_check_mlp2_call(call, &q, state, steps, outputs_present, info, extra);
+}
+
 // What the entry points share once the family's args are in place: `ev` for an evaluation (out / actions_out unused),
-// `out` and `actions_out` for a recording call.
-static inline int bsx_torso_call(bsx_torso_args& a, int32_t family, const bsx_call_t* call, const bsx_mlp2_t* m, bool record,
-                                 const bsx_linear_eval_t& ev, const bsx_timestep_t& out, int32_t* actions_out) {
+// `out` and `actions_out` for a recording call; `mode` BSX_TORSO_GREEDY (inv_temperature unused) or BSX_TORSO_DRAWN
+// (m->explore_seed is the sample seed, m->epsilon is 0.0).
+static inline int bsx_torso_call(bsx_torso_args& a, int32_t family, const bsx_call_t* call, const bsx_mlp2_t* m, int32_t mode,
+                                 double inv_temperature, bool record, const bsx_linear_eval_t& ev, const bsx_timestep_t& out,
+                                 int32_t* actions_out) {
   a.family = family;
   a.n_steps = call->n_steps;
-  a.mode = BSX_TORSO_GREEDY;
+  a.mode = mode;
   a.record = record ? 1 : 0;
   a.p.w1 = m->w1; a.p.w2 = m->w2; a.p.w3 = m->w3;
   a.p.policy_index = m->n_policies > 1 ? m->policy_index : nullptr;
   a.p.observation_in = m->observation_in;
-  a.p.epsilon = m->epsilon;
+  a.p.epsilon = mode == BSX_TORSO_DRAWN ? 0.0 : m->epsilon;
   a.p.explore_seed = m->explore_seed;
   a.p.n_policies = m->n_policies; a.p.hidden1 = m->hidden1; a.p.hidden2 = m->hidden2;
   a.p.width = bsx_torso_width(m->hidden2);
   a.ev = ev; a.out = out; a.actions_out = actions_out;
+  a.beta = mode == BSX_TORSO_DRAWN ? inv_temperature : 1.0;
   return bsx_launch_torso(a, (hipStream_t)call->hip_stream);
 }
 

@@ -99,30 +99,45 @@ extern "C" int bsx_cartpole_mlp_rollout(const bsx_cartpole_t* cfg, const bsx_cal
   return cartpole_trajectory(cfg, call, mlp, state, steps, out, actions_out, info);
 }
 
-// evaluate_mlp2 / rollout_mlp2: the closed loop under a policy with two ReLU hidden layers, returns only or recorded.
-static int cartpole_torso(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, float* state, int32_t* steps,
-                          bool record, const bsx_linear_eval_t& ev, const bsx_timestep_t& out, int32_t* actions_out, double* info) {
+// evaluate_mlp2 / rollout_mlp2 (BSX_TORSO_GREEDY) and evaluate_sampled_mlp2 / sample_mlp2 (BSX_TORSO_DRAWN): the closed loop
+// under a policy with two ReLU hidden layers, returns only or recorded.
+static int cartpole_torso(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, int32_t mode,
+                          double inv_temperature, float* state, int32_t* steps, bool record, const bsx_linear_eval_t& ev,
+                          const bsx_timestep_t& out, int32_t* actions_out, double* info) {
   if (cfg == nullptr || call == nullptr || mlp2 == nullptr) return BSX_ENULL;
   bsx_torso_args e;
   cartpole_env::args* a = &e.fam.cartpole;
   int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
   const bool present = record ? bsx_trajectory_outputs_present(out, actions_out) : bsx_linear_eval_present(ev);
-  if (rc == 0) rc = bsx_check_mlp2_call(call, mlp2, state, steps, present, info, cfg->time_frac);
+  if (rc == 0)
+    rc = mode == BSX_TORSO_DRAWN ? bsx_check_mlp2_sample_call(call, mlp2, inv_temperature, state, steps, present, info, cfg->time_frac)
+                                 : bsx_check_mlp2_call(call, mlp2, state, steps, present, info, cfg->time_frac);
   if (record) rc = bsx_check_trajectory_slab(rc, call, cfg->swingup ? 8 : 6);
   if (rc != 0 || call->n_lanes == 0) return rc;
   a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.out)
   a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_torso_call(e, BSX_FAM_CARTPOLE, call, mlp2, record, ev, out, actions_out);
+  return bsx_torso_call(e, BSX_FAM_CARTPOLE, call, mlp2, mode, inv_temperature, record, ev, out, actions_out);
 }
 
 extern "C" int bsx_cartpole_mlp2_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, float* state,
                                            int32_t* steps, bsx_linear_eval_t out, double* info) {
-  return cartpole_torso(cfg, call, mlp2, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
+  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
 }
 
 extern "C" int bsx_cartpole_mlp2_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, float* state,
                                           int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return cartpole_torso(cfg, call, mlp2, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+}
+
+extern "C" int bsx_cartpole_mlp2_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, double inv_temperature,
+                                         float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+}
+
+extern "C" int bsx_cartpole_mlp2_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                                  double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                                  double* info) {
+  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
 }
 
 // sample_linear / sample_mlp: the recording closed loop with actions drawn from softmax(logits * inv_temperature).

@@ -81,31 +81,48 @@ extern "C" int bsx_mountain_car_mlp_rollout(const bsx_mountain_car_t* cfg, const
   return mountain_car_trajectory(cfg, call, mlp, state, steps, out, actions_out, info);
 }
 
-// evaluate_mlp2 / rollout_mlp2: the closed loop under a policy with two ReLU hidden layers, returns only or recorded.
-static int mountain_car_torso(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, float* state,
-                              int32_t* steps, bool record, const bsx_linear_eval_t& ev, const bsx_timestep_t& out,
-                              int32_t* actions_out, double* info) {
+// evaluate_mlp2 / rollout_mlp2 (BSX_TORSO_GREEDY) and evaluate_sampled_mlp2 / sample_mlp2 (BSX_TORSO_DRAWN): the closed loop
+// under a policy with two ReLU hidden layers, returns only or recorded.
+static int mountain_car_torso(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, int32_t mode,
+                              double inv_temperature, float* state, int32_t* steps, bool record, const bsx_linear_eval_t& ev,
+                              const bsx_timestep_t& out, int32_t* actions_out, double* info) {
   if (cfg == nullptr || call == nullptr || mlp2 == nullptr) return BSX_ENULL;
   int rc = (cfg->max_steps < 1 || cfg->max_steps >= (1 << 30)) ? BSX_ERANGE : 0;
   const bool present = record ? bsx_trajectory_outputs_present(out, actions_out) : bsx_linear_eval_present(ev);
-  if (rc == 0) rc = bsx_check_mlp2_call(call, mlp2, state, steps, present, info, cfg);
+  if (rc == 0)
+    rc = mode == BSX_TORSO_DRAWN ? bsx_check_mlp2_sample_call(call, mlp2, inv_temperature, state, steps, present, info, cfg)
+                                 : bsx_check_mlp2_call(call, mlp2, state, steps, present, info, cfg);
   if (record) rc = bsx_check_trajectory_slab(rc, call, 3);
   if (rc != 0 || call->n_lanes == 0) return rc;
   bsx_torso_args e;
   mountain_car_env::args* a = &e.fam.mountain_car;
   a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.out)
   a->info = info; a->obs_numel = 3; a->max_steps = cfg->max_steps;
-  return bsx_torso_call(e, BSX_FAM_MOUNTAIN_CAR, call, mlp2, record, ev, out, actions_out);
+  return bsx_torso_call(e, BSX_FAM_MOUNTAIN_CAR, call, mlp2, mode, inv_temperature, record, ev, out, actions_out);
 }
 
 extern "C" int bsx_mountain_car_mlp2_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
                                                float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
-  return mountain_car_torso(cfg, call, mlp2, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
+  return mountain_car_torso(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
 }
 
 extern "C" int bsx_mountain_car_mlp2_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
                                               float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return mountain_car_torso(cfg, call, mlp2, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+  return mountain_car_torso(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+}
+
+extern "C" int bsx_mountain_car_mlp2_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                             double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                                             int32_t* actions_out, double* info) {
+  return mountain_car_torso(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps, true, bsx_linear_eval_t{}, out, actions_out,
+                            info);
+}
+
+extern "C" int bsx_mountain_car_mlp2_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                                      double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                                      double* info) {
+  return mountain_car_torso(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps, false, out, bsx_timestep_t{}, nullptr,
+                            info);
 }
 
 // sample_linear / sample_mlp: the recording closed loop with actions drawn from softmax(logits * inv_temperature).

@@ -1729,6 +1729,72 @@ class Environment(dm_env.EnvironmentBase):
     self._launch_steps(getattr(_native.lib, self._mlp_sample_eval_abi), args, int(num_steps), what)
     return ev
 
+  _mlp2_sample_abi = None          # subclass: the C-ABI entry points of sample_mlp2 / evaluate_sampled_mlp2 (cartpole,
+  _mlp2_sample_eval_abi = None     # swing-up, mountain_car)
+
+  def sample_mlp2(self, w1, w2, w3, observation, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`sample_mlp` for an agent with TWO ReLU hidden layers — `rollout_mlp2` with actions drawn from the softmax of its
+    logits: the same ONE launch, the same `(ts, actions)`, contract and refusals.  The call equals, bit for bit in everything
+    it returns and everything it leaves behind,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(mlp2_logits(w1[row], w2[row], w3[row], obs), words(sample_seed, lane, call index), temperature)
+                           ts[t] = step(a); actions[t] = a; obs = ts[t].observation
+
+    w1: float32 device tensor [H1, D+1] or [P, H1, D+1]; w2: [H2, H1+1] or [P, H2, H1+1]; w3: [3, H2+1] or [P, 3, H2+1],
+    1 <= H1, H2 <= 64, each `torch.cat([lin.weight, lin.bias[:, None]], 1)` of a `torch.nn.Linear`; `policy_index` (clamped
+    to [0, P-1]) and `observation` as in rollout_mlp2; temperature and sample_seed as in sample_linear
+    (utils.observations.mlp2_logits and gumbel_select have the rule): a finite temperature > 0 whose inverse is finite, no
+    epsilon and no greedy limit (rollout_mlp2).  The words are words 0..2 of stream 3 of (sample_seed, global lane id, call
+    index); nothing is drawn on a step that resets, and a lane that resets on the first step never reads its row of
+    `observation`.  A -inf logit masks its action; a NaN score never wins, and a NaN score of action 0 is never beaten.  A
+    shared triple is kept on chip; a population is read from device memory by every lane on every step: group the lanes by
+    policy.  `rollout(actions)` on a twin reproduces `ts`.  State, bsuite_info(), episode_counters() and the call index are
+    left as T step() calls leave them.  Output buffers are cached per T, shared with the other sample_* and the rollout_*
+    calls, and overwritten by the next call of the same T."""
+    what = 'sample_mlp2'
+    P, H1, H2 = self._check_evaluate_mlp2(w1, w2, w3, observation, num_steps, policy_index, 0.0, 0, what=what, abi='_mlp2_sample_abi')
+    beta = self._check_sample(what, temperature, sample_seed)
+    self._check_trajectory_slab(what)
+    self._ensure_allocated()
+    T = int(num_steps)
+    _, ptrs, timestep, actions = self._trajectory_out(T)
+    mlp2 = self._mlp2_struct(w1, w2, w3, H1, H2, P, policy_index, 0.0, int(sample_seed), observation)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp2), beta) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (ptrs, actions.data_ptr(), self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp2_sample_abi), args, T, what)
+    return timestep, actions
+
+  def evaluate_sampled_mlp2(self, w1, w2, w3, observation, num_steps, *, policy_index=None, temperature=1.0, sample_seed=0):
+    """`evaluate_sampled_mlp` for an agent with TWO ReLU hidden layers — `sample_mlp2` with the same arguments, returns only:
+    the same ONE launch, the same steps and draws, the same `LinearEvaluation`, contract and refusals.  The call equals, bit
+    for bit in everything it leaves behind and returns,
+
+        obs = observation
+        for t in range(T): a = 0 where the lane resets on this call, else
+                               gumbel_select(mlp2_logits(w1[row], w2[row], w3[row], obs), words(sample_seed, lane, call index), temperature)
+                           ts = step(a); obs = ts.observation
+
+    w1: float32 device tensor [H1, D+1] or [P, H1, D+1]; w2: [H2, H1+1] or [P, H2, H1+1]; w3: [3, H2+1] or [P, 3, H2+1],
+    1 <= H1, H2 <= 64, each `torch.cat([lin.weight, lin.bias[:, None]], 1)` of a `torch.nn.Linear`; `policy_index` and
+    `observation` as in sample_mlp2; temperature and sample_seed as in sample_linear.  A shared triple is kept on chip; a
+    population is read from device memory by every lane on every step: group the lanes by policy.  State, bsuite_info(),
+    episode_counters(), invalid_action_count() and the call index are left bit for bit where sample_mlp2 leaves them; no
+    TimeStep is written, and there is no 4 GiB slab refusal (no slab is written).  The result buffers are the ones
+    evaluate_linear() uses, overwritten by the next call of any evaluate_* / evaluate_sampled_* call on this family."""
+    what = 'evaluate_sampled_mlp2'
+    P, H1, H2 = self._check_evaluate_mlp2(w1, w2, w3, observation, num_steps, policy_index, 0.0, 0, what=what,
+                                          abi='_mlp2_sample_eval_abi')
+    beta = self._check_sample(what, temperature, sample_seed)
+    self._ensure_allocated()
+    ev, out = self._fused_eval_out()
+    mlp2 = self._mlp2_struct(w1, w2, w3, H1, H2, P, policy_index, 0.0, int(sample_seed), observation)
+    args = (ctypes.byref(self._cfg), ctypes.byref(self._call_desc), ctypes.byref(mlp2), beta) + \
+        tuple(t.data_ptr() for t in self._state.values()) + (out, self._info.data_ptr())
+    self._launch_steps(getattr(_native.lib, self._mlp2_sample_eval_abi), args, int(num_steps), what)
+    return ev
+
   def _step(self, action):
     raise NotImplementedError('The batched engine fuses _step/_reset into one kernel; call step().')
 

@@ -80,6 +80,8 @@ class _CartpoleBase(base.Environment):
   _mlp_sample_abi = 'bsx_cartpole_mlp_sample'
   _linear_sample_eval_abi = 'bsx_cartpole_linear_sample_evaluate'
   _mlp_sample_eval_abi = 'bsx_cartpole_mlp_sample_evaluate'
+  _mlp2_sample_abi = 'bsx_cartpole_mlp2_sample'
+  _mlp2_sample_eval_abi = 'bsx_cartpole_mlp2_sample_evaluate'
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

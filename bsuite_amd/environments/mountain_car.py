@@ -38,6 +38,8 @@ class MountainCar(base.Environment):
   _mlp_sample_abi = 'bsx_mountain_car_mlp_sample'
   _linear_sample_eval_abi = 'bsx_mountain_car_linear_sample_evaluate'
   _mlp_sample_eval_abi = 'bsx_mountain_car_mlp_sample_evaluate'
+  _mlp2_sample_abi = 'bsx_mountain_car_mlp2_sample'
+  _mlp2_sample_eval_abi = 'bsx_mountain_car_mlp2_sample_evaluate'
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

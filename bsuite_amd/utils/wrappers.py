@@ -114,6 +114,20 @@ class _RewardWrapper(dm_env.EnvironmentBase):
     raise ValueError(f'rollout_mlp2() is not available through {type(self).__name__}: the fused two-hidden-layer rollout has no '
                      'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
 
+  def sample_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused, like rollout_mlp2: the sampled trajectory records the raw environment's rewards (base.Environment.sample_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError(f'sample_mlp2() is not available through {type(self).__name__}: the fused sampled two-hidden-layer rollout has '
+                     'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def evaluate_sampled_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused, like evaluate_mlp2: the sampled evaluation sums the raw environment's rewards
+    (base.Environment.evaluate_sampled_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError(f'evaluate_sampled_mlp2() is not available through {type(self).__name__}: the fused sampled two-hidden-layer '
+                     'evaluation has no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / '
+                     'MountainCar')
+
   def sample_linear(self, weights, observation, num_steps, **kwargs):
     """Refused, like rollout_linear: the sampled trajectory records the raw environment's rewards (base.Environment.sample_linear)."""
     del weights, observation, num_steps, kwargs
@@ -639,6 +653,21 @@ class ImageObservation(dm_env.EnvironmentBase):
     del w1, w2, w3, observation, num_steps, kwargs
     raise ValueError('rollout_mlp2() is not available through ImageObservation: the fused two-hidden-layer rollout selects its actions '
                      'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def sample_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused: the sampled two-hidden-layer rollout returns the raw environment's float rows, never images
+    (base.Environment.sample_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError('sample_mlp2() is not available through ImageObservation: the fused sampled two-hidden-layer rollout draws its '
+                     'actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
+
+  def evaluate_sampled_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
+    """Refused: the sampled two-hidden-layer evaluation draws its actions from the raw environment's float rows, never images
+    (base.Environment.evaluate_sampled_mlp2)."""
+    del w1, w2, w3, observation, num_steps, kwargs
+    raise ValueError('evaluate_sampled_mlp2() is not available through ImageObservation: the fused sampled two-hidden-layer '
+                     'evaluation draws its actions from, and returns, the raw observation rows; call it on an un-wrapped '
+                     'Cartpole / CartpoleSwingup / MountainCar')
 
   def sample_linear(self, weights, observation, num_steps, **kwargs):
     """Refused: the sampled linear rollout returns the raw environment's float rows, never images (base.Environment.sample_linear)."""

@@ -755,6 +755,38 @@ int bsx_cartpole_mlp2_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call,
 int bsx_mountain_car_mlp2_rollout(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
                                   float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info);
 
+/* ---- two hidden layers, sampled: the two calls above with a softmax policy (cartpole, swing-up, mountain_car; v12,
+ *      additive) --------------------------------------------------------------------------------
+ * bsx_<family>_mlp2_rollout / bsx_<family>_mlp2_evaluate with the same policy struct, outputs, reset rule and refusals, in
+ * ONE launch — but the action of a lane that does not reset is a draw from softmax(inv_temperature * logits) instead of
+ * the greedy one: what bsx_<family>_mlp_sample / bsx_<family>_mlp_sample_evaluate are to bsx_<family>_mlp_rollout /
+ * bsx_<family>_mlp_evaluate.  The logits are exactly the l_a of the greedy rule above (csrc/bsx_mlp2.h); the draw is the
+ * Gumbel-max of the sampled calls (csrc/bsx_gumbel.h):
+ *     u_a = ((double)word_a + 0.5) * 2^-32;  g_a = -bsx_log(-bsx_log(u_a));  z_a = (double)l_a * inv_temperature + g_a
+ *     argmax_a z_a, the lowest index wins a tie and a NaN never wins (a -inf logit masks its action)
+ * with word_a = word a of block 0 of stream 3 (BSX_STREAM_SAMPLE) of (explore_seed, global lane id, call index): the
+ * policy struct's explore_seed is the SAMPLE SEED of these calls.  A lane that resets takes action 0 and draws nothing; a
+ * lane that resets on the first step never reads its row of observation_in.  bsx_<family>_mlp2_sample writes `out` and
+ * actions_out [n_steps, n_lanes]: bsx_<family>_step with n_steps and actions_out as its actions reproduces `out`.
+ * bsx_<family>_mlp2_sample_evaluate writes what bsx_<family>_mlp2_evaluate writes, and leaves state, steps, info, counters
+ * and the call index bit for bit as bsx_<family>_mlp2_sample with the same arguments leaves them.
+ * There is no greedy limit and no epsilon: BSX_ERANGE — where the greedy calls refuse an epsilon outside [0, 1]: after the
+ * modes and the scalars (hidden1 / hidden2 included), before an empty call returns and before any pointer is looked at —
+ * if the struct's epsilon is not 0.0 (NaN included) or inv_temperature is not a finite number > 0.  Every other refusal,
+ * and their order, is that of the greedy calls; the 4 GiB slab is refused by the recording call alone. */
+int bsx_cartpole_mlp2_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                             double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                             int32_t* actions_out, double* info);
+int bsx_mountain_car_mlp2_sample(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                 double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
+                                 int32_t* actions_out, double* info);
+int bsx_cartpole_mlp2_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                      double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                      double* info);
+int bsx_mountain_car_mlp2_sample_evaluate(const bsx_mountain_car_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                          double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
+                                          double* info);
+
 /* ---- mnist bandit : bsuite/environments/mnist.py:33-89, bsuite/utils/datasets.py:42-69 -------- */
 typedef struct {
   int32_t num_data;        /* int(fraction * len(labels)) (mnist.py:46-48); 1..2^24               */
