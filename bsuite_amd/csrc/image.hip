@@ -21,7 +21,9 @@
 //   weights (1 - (cc - f), cc - f) on source indices mirror(f), mirror(f + 1);
 //   t = 0 + (v00*wy0)*wx0 + (v01*wy0)*wx1 + (v10*wy1)*wx0 + (v11*wy1)*wx1;  out = (float)t
 // (the f64 uint8 path takes scipy's own second weight 1 - (1 - (cc - f)), see img_axis_entry)
-// (pinned bit for bit against scipy in tests/test_image_oracle.py, tests/test_gpu_adapters.py and tests/test_gpu_image_dtype.py).
+// (pinned bit for bit against scipy in tests/test_image_oracle.py, tests/test_gpu_adapters.py and tests/test_gpu_image_dtype.py;
+// tests/test_gpu_image_edges.py holds the edges: filters wider than their axis, more than 64 KiB of LDS, every store
+// branch of every output type over several workgroups, ties, overflow, subnormals, signed zeros, inf and NaN).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -10,7 +10,7 @@ preserve_range=True)`, i.e. order=1, mode='reflect', clip=True, anti_aliasing=No
     `scipy.ndimage.gaussian_filter(image, sigma, cval=cval, mode='mirror')`;
   * `scipy.ndimage.zoom(image, 1/factors, order=1, mode='mirror', grid_mode=True)`
     ('reflect' in numpy.pad vocabulary is ndimage's 'mirror');
-  * the result is clipped to the input's [min, max].
+  * the result is clipped to the input's [min, max] ([nanmin, nanmax] when the input holds a NaN).
 
 Parity with a real skimage is UNPINNED — only scipy.ndimage, which skimage delegates to, is present
 here; the control flow above is transcribed from skimage/transform/_warps.py (resize, 0.19-0.22).
@@ -42,6 +42,11 @@ def resize(image, output_shape, order=None, mode='reflect', cval=0, clip=True, p
     filtered = image
   zoom_factors = [1 / f for f in factors]
   out = ndi.zoom(filtered, zoom_factors, order=1, mode='mirror', cval=cval, grid_mode=True)
-  if clip:
-    np.clip(out, np.min(image), np.max(image), out=out)
+  if clip:                                # _clip_warp_output: NaN-safe bounds when the plain range is NaN
+    min_val = np.min(image)
+    if np.isnan(min_val):
+      min_val, max_val = np.nanmin(image), np.nanmax(image)
+    else:
+      max_val = np.max(image)
+    np.clip(out, min_val, max_val, out=out)
   return out
