@@ -254,41 +254,6 @@ _SIGS = {
                                  ctypes.c_int),
     'bsx_catch_step': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                        ctypes.c_int),
-    'bsx_deep_sea_policy_rollout': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
-                                     TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_catch_policy_rollout': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
-                                  TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_deep_sea_policy_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
-                                      PolicyEvalPtrs, _P], ctypes.c_int),
-    'bsx_catch_policy_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(Policy), _P,
-                                   PolicyEvalPtrs, _P], ctypes.c_int),
-    # sample_policy / evaluate_sampled_policy: the signatures of *_policy_rollout / *_policy_evaluate with a table of logits
-    'bsx_deep_sea_policy_sample': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
-                                    TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_catch_policy_sample': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
-                                 TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_deep_sea_policy_sample_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
-                                             PolicyEvalPtrs, _P], ctypes.c_int),
-    'bsx_catch_policy_sample_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyLogits), _P,
-                                          PolicyEvalPtrs, _P], ctypes.c_int),
-    # rollout_embedding / evaluate_embedding: the signatures of *_policy_rollout / *_policy_evaluate with a pair of matrices
-    'bsx_deep_sea_embedding_rollout': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
-                                        TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_catch_embedding_rollout': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
-                                     TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_deep_sea_embedding_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
-                                         PolicyEvalPtrs, _P], ctypes.c_int),
-    'bsx_catch_embedding_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbedding), _P,
-                                      PolicyEvalPtrs, _P], ctypes.c_int),
-    # sample_embedding / evaluate_sampled_embedding: the same signatures with the sampled pair of matrices
-    'bsx_deep_sea_embedding_sample': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample), _P,
-                                       TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_catch_embedding_sample': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample), _P,
-                                    TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_deep_sea_embedding_sample_evaluate': ([ctypes.POINTER(DeepSeaCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample),
-                                                _P, PolicyEvalPtrs, _P], ctypes.c_int),
-    'bsx_catch_embedding_sample_evaluate': ([ctypes.POINTER(CatchCfg), ctypes.POINTER(Call), ctypes.POINTER(PolicyEmbeddingSample), _P,
-                                             PolicyEvalPtrs, _P], ctypes.c_int),
     'bsx_bandit_step': ([ctypes.POINTER(BanditCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                         ctypes.c_int),
     'bsx_memory_chain_step': ([ctypes.POINTER(MemoryChainCfg), ctypes.POINTER(Call), _P, _P, _P,
@@ -299,40 +264,31 @@ _SIGS = {
                                     TimeStepPtrs], ctypes.c_int),
     'bsx_cartpole_step': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), _P, _P, _P,
                            TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_cartpole_linear_evaluate': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), ctypes.POINTER(Linear), _P, _P,
-                                      LinearEvalPtrs, _P], ctypes.c_int),
-    'bsx_cartpole_mlp_evaluate': ([ctypes.POINTER(CartpoleCfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp), _P, _P,
-                                   LinearEvalPtrs, _P], ctypes.c_int),
     'bsx_mnist_step': ([ctypes.POINTER(MnistCfg), ctypes.POINTER(Call), _P, _P, TimeStepPtrs, _P],
                        ctypes.c_int),
     'bsx_mountain_car_step': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), _P, _P, _P,
                                TimeStepPtrs, _P], ctypes.c_int),
-    'bsx_mountain_car_linear_evaluate': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), ctypes.POINTER(Linear), _P, _P,
-                                          LinearEvalPtrs, _P], ctypes.c_int),
-    'bsx_mountain_car_mlp_evaluate': ([ctypes.POINTER(MountainCarCfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp), _P, _P,
-                                       LinearEvalPtrs, _P], ctypes.c_int),
 }
-# rollout_linear / rollout_mlp: the evaluation's arguments with a [T,B] TimeStep and the action column as the outputs
+# The fused closed-loop calls: bsx_<family>_<kind>_<rollout|evaluate|sample|sample_evaluate>.
+# The grids (rollout_policy ... evaluate_sampled_embedding): configuration, call, the policy struct — greedy calls one type, drawn
+# calls another; it carries the action column and, drawn calls, the inverse temperature — the state column, the outputs
+# (a [T,B] TimeStep, or the three result columns), info.
+for _fam, _cfg in (('deep_sea', DeepSeaCfg), ('catch', CatchCfg)):
+  for _kind, _greedy, _drawn in (('policy', Policy, PolicyLogits), ('embedding', PolicyEmbedding, PolicyEmbeddingSample)):
+    for _verb, _policy, _out in (('rollout', _greedy, TimeStepPtrs), ('evaluate', _greedy, PolicyEvalPtrs),
+                                 ('sample', _drawn, TimeStepPtrs), ('sample_evaluate', _drawn, PolicyEvalPtrs)):
+      _SIGS[f'bsx_{_fam}_{_kind}_{_verb}'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy), _P, _out, _P],
+                                              ctypes.c_int)
+# The physics families (evaluate_linear ... evaluate_sampled_mlp2): configuration, call, the policy struct, `double
+# inv_temperature` (drawn calls only), the two state columns, the outputs (a [T,B] TimeStep and the action column, or the
+# three result columns and the final observation rows), info.
 for _fam, _cfg in (('cartpole', CartpoleCfg), ('mountain_car', MountainCarCfg)):
-  for _kind, _policy in (('linear', Linear), ('mlp', Mlp)):
-    _SIGS[f'bsx_{_fam}_{_kind}_rollout'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy), _P, _P,
-                                             TimeStepPtrs, _P, _P], ctypes.c_int)
-    # sample_linear / sample_mlp: the recording call's arguments with `double inv_temperature` after the policy struct
-    _SIGS[f'bsx_{_fam}_{_kind}_sample'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy), ctypes.c_double,
-                                            _P, _P, TimeStepPtrs, _P, _P], ctypes.c_int)
-    # evaluate_sampled_linear / evaluate_sampled_mlp: the evaluation's arguments with `double inv_temperature` after the struct
-    _SIGS[f'bsx_{_fam}_{_kind}_sample_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy),
-                                                     ctypes.c_double, _P, _P, LinearEvalPtrs, _P], ctypes.c_int)
-  # evaluate_mlp2 / rollout_mlp2: the signatures of *_mlp_evaluate / *_mlp_rollout with the triple of matrices
-  _SIGS[f'bsx_{_fam}_mlp2_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), _P, _P,
-                                         LinearEvalPtrs, _P], ctypes.c_int)
-  _SIGS[f'bsx_{_fam}_mlp2_rollout'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), _P, _P,
-                                        TimeStepPtrs, _P, _P], ctypes.c_int)
-  # sample_mlp2 / evaluate_sampled_mlp2: the signatures of *_mlp_sample / *_mlp_sample_evaluate with the triple of matrices
-  _SIGS[f'bsx_{_fam}_mlp2_sample'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2), ctypes.c_double,
-                                       _P, _P, TimeStepPtrs, _P, _P], ctypes.c_int)
-  _SIGS[f'bsx_{_fam}_mlp2_sample_evaluate'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(Mlp2),
-                                                ctypes.c_double, _P, _P, LinearEvalPtrs, _P], ctypes.c_int)
+  for _kind, _policy in (('linear', Linear), ('mlp', Mlp), ('mlp2', Mlp2)):
+    for _verb, _beta, _out in (('rollout', [], [TimeStepPtrs, _P]), ('evaluate', [], [LinearEvalPtrs]),
+                               ('sample', [ctypes.c_double], [TimeStepPtrs, _P]),
+                               ('sample_evaluate', [ctypes.c_double], [LinearEvalPtrs])):
+      _SIGS[f'bsx_{_fam}_{_kind}_{_verb}'] = ([ctypes.POINTER(_cfg), ctypes.POINTER(Call), ctypes.POINTER(_policy)] + _beta
+                                              + [_P, _P] + _out + [_P], ctypes.c_int)
 _G = ctypes.c_void_p   # bsx_group_t*
 _SIGS.update({
     'bsx_group_create': ([ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_G)], ctypes.c_int),

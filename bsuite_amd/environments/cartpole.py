@@ -70,18 +70,7 @@ class _CartpoleBase(base.Environment):
                 steps=torch.full((self._batch,), 1 << 30, dtype=torch.int32, device=self._device))
 
   _abi_name = 'cartpole'
-  _linear_eval_abi = 'bsx_cartpole_linear_evaluate'
-  _mlp_eval_abi = 'bsx_cartpole_mlp_evaluate'
-  _linear_rollout_abi = 'bsx_cartpole_linear_rollout'
-  _mlp_rollout_abi = 'bsx_cartpole_mlp_rollout'
-  _mlp2_eval_abi = 'bsx_cartpole_mlp2_evaluate'
-  _mlp2_rollout_abi = 'bsx_cartpole_mlp2_rollout'
-  _linear_sample_abi = 'bsx_cartpole_linear_sample'
-  _mlp_sample_abi = 'bsx_cartpole_mlp_sample'
-  _linear_sample_eval_abi = 'bsx_cartpole_linear_sample_evaluate'
-  _mlp_sample_eval_abi = 'bsx_cartpole_mlp_sample_evaluate'
-  _mlp2_sample_abi = 'bsx_cartpole_mlp2_sample'
-  _mlp2_sample_eval_abi = 'bsx_cartpole_mlp2_sample_evaluate'
+  _closed_loop_kinds = ('linear', 'mlp', 'mlp2')
 
   def action_spec(self):
     return specs.DiscreteArray(dtype=int, num_values=3, name='action')

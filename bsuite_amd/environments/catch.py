@@ -45,14 +45,7 @@ class Catch(base.Environment):
   _index_width = 2
   _pipelined_rollout = True
 
-  _policy_abi = 'bsx_catch_policy_rollout'
-  _policy_eval_abi = 'bsx_catch_policy_evaluate'
-  _policy_sample_abi = 'bsx_catch_policy_sample'
-  _policy_sample_eval_abi = 'bsx_catch_policy_sample_evaluate'
-  _embedding_rollout_abi = 'bsx_catch_embedding_rollout'
-  _embedding_eval_abi = 'bsx_catch_embedding_evaluate'
-  _embedding_sample_abi = 'bsx_catch_embedding_sample'
-  _embedding_sample_eval_abi = 'bsx_catch_embedding_sample_evaluate'
+  _closed_loop_kinds = ('policy', 'embedding')
 
   @property
   def policy_num_states(self) -> int:

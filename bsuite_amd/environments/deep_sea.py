@@ -89,14 +89,7 @@ class DeepSea(base.Environment):
     return (bool(self._deterministic) and (self._size * self._size) % 4 == 0 and not self._scalar and not self._delta
             and not self._index and not self._obs_flags and self._rng_mode == 'philox')
 
-  _policy_abi = 'bsx_deep_sea_policy_rollout'
-  _policy_eval_abi = 'bsx_deep_sea_policy_evaluate'
-  _policy_sample_abi = 'bsx_deep_sea_policy_sample'
-  _policy_sample_eval_abi = 'bsx_deep_sea_policy_sample_evaluate'
-  _embedding_rollout_abi = 'bsx_deep_sea_embedding_rollout'
-  _embedding_eval_abi = 'bsx_deep_sea_embedding_evaluate'
-  _embedding_sample_abi = 'bsx_deep_sea_embedding_sample'
-  _embedding_sample_eval_abi = 'bsx_deep_sea_embedding_sample_evaluate'
+  _closed_loop_kinds = ('policy', 'embedding')
 
   @property
   def policy_num_states(self) -> int:

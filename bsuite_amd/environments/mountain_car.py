@@ -28,18 +28,7 @@ class MountainCar(base.Environment):
                 steps=torch.full((self._batch,), 1 << 30, dtype=torch.int32, device=self._device))
 
   _abi_name = 'mountain_car'
-  _linear_eval_abi = 'bsx_mountain_car_linear_evaluate'
-  _mlp_eval_abi = 'bsx_mountain_car_mlp_evaluate'
-  _linear_rollout_abi = 'bsx_mountain_car_linear_rollout'
-  _mlp_rollout_abi = 'bsx_mountain_car_mlp_rollout'
-  _mlp2_eval_abi = 'bsx_mountain_car_mlp2_evaluate'
-  _mlp2_rollout_abi = 'bsx_mountain_car_mlp2_rollout'
-  _linear_sample_abi = 'bsx_mountain_car_linear_sample'
-  _mlp_sample_abi = 'bsx_mountain_car_mlp_sample'
-  _linear_sample_eval_abi = 'bsx_mountain_car_linear_sample_evaluate'
-  _mlp_sample_eval_abi = 'bsx_mountain_car_mlp_sample_evaluate'
-  _mlp2_sample_abi = 'bsx_mountain_car_mlp2_sample'
-  _mlp2_sample_eval_abi = 'bsx_mountain_car_mlp2_sample_evaluate'
+  _closed_loop_kinds = ('linear', 'mlp', 'mlp2')
 
   def _pending_info(self):
     # every step pays -1 (mountain_car.py:75-76): a running episode of t steps has earned -t; the

@@ -28,6 +28,58 @@ from bsuite_amd import dm_env_compat as dm_env
 from bsuite_amd.environments import base
 
 
+# The fused closed-loop calls of base.Environment run the raw environment's kernel: without a reward wrapper's epilogue,
+# without Logging, on index observations or raw observation rows, never on images.  A wrapper that delegated them would
+# drop itself silently, so every wrapper class refuses them (`_refusing`).  Per class, call name -> the middle of its message.
+_REWARD_REFUSALS = {
+    'rollout_policy': 'policy rollout', 'evaluate_policy': 'policy evaluation',
+    'sample_policy': 'sampled policy rollout', 'evaluate_sampled_policy': 'sampled policy evaluation',
+    'rollout_embedding': 'hidden-layer rollout', 'evaluate_embedding': 'hidden-layer evaluation',
+    'sample_embedding': 'sampled hidden-layer rollout', 'evaluate_sampled_embedding': 'sampled hidden-layer evaluation',
+    'rollout_linear': 'linear rollout', 'evaluate_linear': 'linear evaluation',
+    'sample_linear': 'sampled rollout', 'evaluate_sampled_linear': 'sampled evaluation',
+    'rollout_mlp': 'hidden-layer rollout', 'evaluate_mlp': 'hidden-layer evaluation',
+    'sample_mlp': 'sampled hidden-layer rollout', 'evaluate_sampled_mlp': 'sampled hidden-layer evaluation',
+    'rollout_mlp2': 'two-hidden-layer rollout', 'evaluate_mlp2': 'two-hidden-layer evaluation',
+    'sample_mlp2': 'sampled two-hidden-layer rollout', 'evaluate_sampled_mlp2': 'sampled two-hidden-layer evaluation',
+}
+_IMAGE_REFUSALS = {
+    'rollout_policy': 'policy rollout returns index observations',
+    'evaluate_policy': 'policy evaluation looks its actions up by index observations',
+    'sample_policy': 'sampled policy rollout returns index observations',
+    'evaluate_sampled_policy': 'sampled policy evaluation looks its logits up by index observations',
+    'rollout_embedding': 'hidden-layer rollout returns index observations',
+    'evaluate_embedding': 'hidden-layer evaluation gathers its first layer by index observations',
+    'sample_embedding': 'sampled hidden-layer rollout returns index observations',
+    'evaluate_sampled_embedding': 'sampled hidden-layer evaluation gathers its first layer by index observations',
+    'rollout_linear': 'linear rollout selects its actions from, and returns, the raw observation rows',
+    'evaluate_linear': 'linear evaluation selects its actions from the raw observation rows',
+    'sample_linear': 'sampled rollout draws its actions from, and returns, the raw observation rows',
+    'evaluate_sampled_linear': 'sampled evaluation draws its actions from, and returns, the raw observation rows',
+    'rollout_mlp': 'hidden-layer rollout selects its actions from, and returns, the raw observation rows',
+    'evaluate_mlp': 'hidden-layer evaluation selects its actions from the raw observation rows',
+    'sample_mlp': 'sampled hidden-layer rollout draws its actions from, and returns, the raw observation rows',
+    'evaluate_sampled_mlp': 'sampled hidden-layer evaluation draws its actions from, and returns, the raw observation rows',
+    'rollout_mlp2': 'two-hidden-layer rollout selects its actions from, and returns, the raw observation rows',
+    'evaluate_mlp2': 'two-hidden-layer evaluation selects its actions from the raw observation rows',
+    'sample_mlp2': 'sampled two-hidden-layer rollout draws its actions from, and returns, the raw observation rows',
+    'evaluate_sampled_mlp2': 'sampled two-hidden-layer evaluation draws its actions from, and returns, the raw observation rows',
+}
+
+
+def _refusing(name, middle):
+  """The method a wrapper class has in place of the fused call `name`: it takes the call's arguments without looking at
+  them and raises."""
+  families = 'DeepSea / Catch' if name.endswith(('_policy', '_embedding')) else 'Cartpole / CartpoleSwingup / MountainCar'
+
+  def refuse(self, *args, **kwargs):
+    del args, kwargs
+    raise ValueError(f'{name}() is not available through {type(self).__name__}: the fused {middle}; call it on an un-wrapped '
+                     f'{families}')
+  refuse.__name__ = name
+  refuse.__doc__ = f'Refused, never delegated: base.Environment.{name} runs the raw environment alone, without this wrapper.'
+  return refuse
+
 class _RewardWrapper(dm_env.EnvironmentBase):
   """Shared surface of the two reward wrappers."""
 
@@ -65,135 +117,8 @@ class _RewardWrapper(dm_env.EnvironmentBase):
   def rollout(self, actions):
     return self._env.rollout(actions)
 
-  def rollout_policy(self, policy, num_steps, **kwargs):
-    """Refused: the fused policy rollout runs the raw environment's kernel, without this wrapper's epilogue
-    (base.Environment.rollout_policy).  Delegating would drop the wrapper silently."""
-    del policy, num_steps, kwargs
-    raise ValueError(f'rollout_policy() is not available through {type(self).__name__}: the fused policy rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_policy(self, policy, num_steps, **kwargs):
-    """Refused, like rollout_policy: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_policy)."""
-    del policy, num_steps, kwargs
-    raise ValueError(f'evaluate_policy() is not available through {type(self).__name__}: the fused policy evaluation has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused, like evaluate_policy: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError(f'evaluate_linear() is not available through {type(self).__name__}: the fused linear evaluation has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused, like evaluate_linear: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError(f'evaluate_mlp() is not available through {type(self).__name__}: the fused hidden-layer evaluation has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def rollout_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused, like evaluate_linear: the fused trajectory records the raw environment's rewards (base.Environment.rollout_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError(f'rollout_linear() is not available through {type(self).__name__}: the fused linear rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def rollout_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused, like evaluate_mlp: the fused trajectory records the raw environment's rewards (base.Environment.rollout_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError(f'rollout_mlp() is not available through {type(self).__name__}: the fused hidden-layer rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused, like evaluate_mlp: the fused evaluation sums the raw environment's rewards (base.Environment.evaluate_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError(f'evaluate_mlp2() is not available through {type(self).__name__}: the fused two-hidden-layer evaluation has '
-                     'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def rollout_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused, like rollout_mlp: the fused trajectory records the raw environment's rewards (base.Environment.rollout_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError(f'rollout_mlp2() is not available through {type(self).__name__}: the fused two-hidden-layer rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused, like rollout_mlp2: the sampled trajectory records the raw environment's rewards (base.Environment.sample_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError(f'sample_mlp2() is not available through {type(self).__name__}: the fused sampled two-hidden-layer rollout has '
-                     'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_sampled_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused, like evaluate_mlp2: the sampled evaluation sums the raw environment's rewards
-    (base.Environment.evaluate_sampled_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError(f'evaluate_sampled_mlp2() is not available through {type(self).__name__}: the fused sampled two-hidden-layer '
-                     'evaluation has no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / '
-                     'MountainCar')
-
-  def sample_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused, like rollout_linear: the sampled trajectory records the raw environment's rewards (base.Environment.sample_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError(f'sample_linear() is not available through {type(self).__name__}: the fused sampled rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused, like rollout_mlp: the sampled trajectory records the raw environment's rewards (base.Environment.sample_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError(f'sample_mlp() is not available through {type(self).__name__}: the fused sampled hidden-layer rollout has '
-                     'no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_policy(self, logits, num_steps, **kwargs):
-    """Refused, like rollout_policy: the sampled rollout records the raw environment's rewards (base.Environment.sample_policy)."""
-    del logits, num_steps, kwargs
-    raise ValueError(f'sample_policy() is not available through {type(self).__name__}: the fused sampled policy rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_sampled_policy(self, logits, num_steps, **kwargs):
-    """Refused, like evaluate_policy: the sampled evaluation sums the raw environment's rewards
-    (base.Environment.evaluate_sampled_policy)."""
-    del logits, num_steps, kwargs
-    raise ValueError(f'evaluate_sampled_policy() is not available through {type(self).__name__}: the fused sampled policy '
-                     'evaluation has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def rollout_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like rollout_policy: the fused rollout records the raw environment's rewards (base.Environment.rollout_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError(f'rollout_embedding() is not available through {type(self).__name__}: the fused hidden-layer rollout has no '
-                     'reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like evaluate_policy: the fused evaluation sums the raw environment's rewards
-    (base.Environment.evaluate_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError(f'evaluate_embedding() is not available through {type(self).__name__}: the fused hidden-layer evaluation '
-                     'has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def sample_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like rollout_embedding: the sampled rollout records the raw environment's rewards
-    (base.Environment.sample_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError(f'sample_embedding() is not available through {type(self).__name__}: the fused sampled hidden-layer rollout '
-                     'has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_sampled_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like evaluate_embedding: the sampled evaluation sums the raw environment's rewards
-    (base.Environment.evaluate_sampled_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError(f'evaluate_sampled_embedding() is not available through {type(self).__name__}: the fused sampled '
-                     'hidden-layer evaluation has no reward wrapper and no Logging; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused, like evaluate_linear: the sampled evaluation sums the raw environment's rewards
-    (base.Environment.evaluate_sampled_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError(f'evaluate_sampled_linear() is not available through {type(self).__name__}: the fused sampled evaluation '
-                     'has no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_sampled_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused, like evaluate_mlp: the sampled evaluation sums the raw environment's rewards
-    (base.Environment.evaluate_sampled_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError(f'evaluate_sampled_mlp() is not available through {type(self).__name__}: the fused sampled hidden-layer '
-                     'evaluation has no reward wrapper and no Logging; call it on an un-wrapped Cartpole / CartpoleSwingup / '
-                     'MountainCar')
+  locals().update({name: _refusing(name, middle + ' has no reward wrapper and no Logging')
+                   for name, middle in _REWARD_REFUSALS.items()})
 
   def observation_spec(self):
     return self._env.observation_spec()
@@ -604,140 +529,7 @@ class ImageObservation(dm_env.EnvironmentBase):
   def step(self, action, reset_mask=None):
     return self._convert(self._env.step(action) if reset_mask is None else self._env.step(action, reset_mask=reset_mask))
 
-  def rollout_policy(self, policy, num_steps, **kwargs):
-    """Refused: a fused policy rollout returns index observations, never images (base.Environment.rollout_policy)."""
-    del policy, num_steps, kwargs
-    raise ValueError('rollout_policy() is not available through ImageObservation: the fused policy rollout returns index '
-                     'observations; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_policy(self, policy, num_steps, **kwargs):
-    """Refused, like rollout_policy: the fused evaluation looks actions up by index observations (base.Environment.evaluate_policy)."""
-    del policy, num_steps, kwargs
-    raise ValueError('evaluate_policy() is not available through ImageObservation: the fused policy evaluation looks its '
-                     'actions up by index observations; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused: the fused linear evaluation reads the raw environment's float rows, never images (base.Environment.evaluate_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError('evaluate_linear() is not available through ImageObservation: the fused linear evaluation selects its '
-                     'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused: the fused hidden-layer evaluation reads the raw environment's float rows, never images (base.Environment.evaluate_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError('evaluate_mlp() is not available through ImageObservation: the fused hidden-layer evaluation selects its '
-                     'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def rollout_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused: the fused linear rollout returns the raw environment's float rows, never images (base.Environment.rollout_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError('rollout_linear() is not available through ImageObservation: the fused linear rollout selects its actions '
-                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def rollout_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused: the fused hidden-layer rollout returns the raw environment's float rows, never images (base.Environment.rollout_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError('rollout_mlp() is not available through ImageObservation: the fused hidden-layer rollout selects its actions '
-                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused: the fused two-hidden-layer evaluation reads the raw environment's float rows, never images
-    (base.Environment.evaluate_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError('evaluate_mlp2() is not available through ImageObservation: the fused two-hidden-layer evaluation selects its '
-                     'actions from the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def rollout_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused: the fused two-hidden-layer rollout returns the raw environment's float rows, never images
-    (base.Environment.rollout_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError('rollout_mlp2() is not available through ImageObservation: the fused two-hidden-layer rollout selects its actions '
-                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused: the sampled two-hidden-layer rollout returns the raw environment's float rows, never images
-    (base.Environment.sample_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError('sample_mlp2() is not available through ImageObservation: the fused sampled two-hidden-layer rollout draws its '
-                     'actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def evaluate_sampled_mlp2(self, w1, w2, w3, observation, num_steps, **kwargs):
-    """Refused: the sampled two-hidden-layer evaluation draws its actions from the raw environment's float rows, never images
-    (base.Environment.evaluate_sampled_mlp2)."""
-    del w1, w2, w3, observation, num_steps, kwargs
-    raise ValueError('evaluate_sampled_mlp2() is not available through ImageObservation: the fused sampled two-hidden-layer '
-                     'evaluation draws its actions from, and returns, the raw observation rows; call it on an un-wrapped '
-                     'Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused: the sampled linear rollout returns the raw environment's float rows, never images (base.Environment.sample_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError('sample_linear() is not available through ImageObservation: the fused sampled rollout draws its actions '
-                     'from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused: the sampled hidden-layer rollout returns the raw environment's float rows, never images (base.Environment.sample_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError('sample_mlp() is not available through ImageObservation: the fused sampled hidden-layer rollout draws its '
-                     'actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / CartpoleSwingup / MountainCar')
-
-  def sample_policy(self, logits, num_steps, **kwargs):
-    """Refused, like rollout_policy: a fused sampled policy rollout returns index observations, never images
-    (base.Environment.sample_policy)."""
-    del logits, num_steps, kwargs
-    raise ValueError('sample_policy() is not available through ImageObservation: the fused sampled policy rollout returns index '
-                     'observations; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_sampled_policy(self, logits, num_steps, **kwargs):
-    """Refused, like evaluate_policy: the fused sampled evaluation looks its logits up by index observations
-    (base.Environment.evaluate_sampled_policy)."""
-    del logits, num_steps, kwargs
-    raise ValueError('evaluate_sampled_policy() is not available through ImageObservation: the fused sampled policy evaluation '
-                     'looks its logits up by index observations; call it on an un-wrapped DeepSea / Catch')
-
-  def rollout_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like rollout_policy: a fused hidden-layer rollout returns index observations, never images
-    (base.Environment.rollout_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError('rollout_embedding() is not available through ImageObservation: the fused hidden-layer rollout returns index '
-                     'observations; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like evaluate_policy: the fused hidden-layer evaluation gathers its first layer by index observations
-    (base.Environment.evaluate_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError('evaluate_embedding() is not available through ImageObservation: the fused hidden-layer evaluation gathers '
-                     'its first layer by index observations; call it on an un-wrapped DeepSea / Catch')
-
-  def sample_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like rollout_embedding: a fused sampled hidden-layer rollout returns index observations, never images
-    (base.Environment.sample_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError('sample_embedding() is not available through ImageObservation: the fused sampled hidden-layer rollout '
-                     'returns index observations; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_sampled_embedding(self, w1, w2, num_steps, **kwargs):
-    """Refused, like evaluate_embedding: the fused sampled hidden-layer evaluation gathers its first layer by index observations
-    (base.Environment.evaluate_sampled_embedding)."""
-    del w1, w2, num_steps, kwargs
-    raise ValueError('evaluate_sampled_embedding() is not available through ImageObservation: the fused sampled hidden-layer '
-                     'evaluation gathers its first layer by index observations; call it on an un-wrapped DeepSea / Catch')
-
-  def evaluate_sampled_linear(self, weights, observation, num_steps, **kwargs):
-    """Refused: the sampled linear evaluation draws its actions from the raw environment's float rows, never images
-    (base.Environment.evaluate_sampled_linear)."""
-    del weights, observation, num_steps, kwargs
-    raise ValueError('evaluate_sampled_linear() is not available through ImageObservation: the fused sampled evaluation draws '
-                     'its actions from, and returns, the raw observation rows; call it on an un-wrapped Cartpole / '
-                     'CartpoleSwingup / MountainCar')
-
-  def evaluate_sampled_mlp(self, w1, w2, observation, num_steps, **kwargs):
-    """Refused: the sampled hidden-layer evaluation draws its actions from the raw environment's float rows, never images
-    (base.Environment.evaluate_sampled_mlp)."""
-    del w1, w2, observation, num_steps, kwargs
-    raise ValueError('evaluate_sampled_mlp() is not available through ImageObservation: the fused sampled hidden-layer '
-                     'evaluation draws its actions from, and returns, the raw observation rows; call it on an un-wrapped '
-                     'Cartpole / CartpoleSwingup / MountainCar')
+  locals().update({name: _refusing(name, middle) for name, middle in _IMAGE_REFUSALS.items()})
 
   def __getattr__(self, attr):
     """Delegate attribute access to underlying environment."""

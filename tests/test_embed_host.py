@@ -272,10 +272,17 @@ def test_signatures_docstrings_and_families():
     assert list(p) == ['self', 'w1', 'w2', 'num_steps', 'policy_index', 'epsilon', 'explore_seed']
     assert [p[k].kind for k in ('policy_index', 'epsilon', 'explore_seed')] == [inspect.Parameter.KEYWORD_ONLY] * 3
     assert p['policy_index'].default is None and p['epsilon'].default == 0.0 and p['explore_seed'].default == 0
-    src = inspect.getsource(fn)
-    assert src.index('_check_embedding(') < src.index('_ensure_allocated()')                          # every refusal first
-  chk = inspect.getsource(base.Environment._check_embedding)                                          # pylint: disable=protected-access
-  assert chk.index('_check_policy_env(') < chk.index('w1 and w2 must be') < chk.index('_check_policy_population(') < chk.index('epsilon must be') < chk.index('explore_seed must be')
+    for env in _envs():                                                                               # every refusal first: the last
+      env._device = torch.device('cpu')                                                               # one of the call allocates nothing
+      _refused(env, name, explore_seed=-1, match='explore_seed must be')
+      # the order, two faults at a time: the environment, the matrices, the population rule, epsilon, the seed
+      idx = torch.zeros(4, dtype=torch.int32)
+      _refused(env, name, w1=None, num_steps=0, match='num_steps')
+      _refused(env, name, w1=None, policy_index=idx, match='w1 and w2 must be')
+      _refused(env, name, policy_index=idx, epsilon=2.0, match='must be None')
+      _refused(env, name, epsilon=2.0, explore_seed=-1, match='epsilon must be')
+      env._logging = dict(steps=None)
+      _refused(env, name, w1=None, num_steps=0, match='Logging')
   doc = base.Environment.rollout_embedding.__doc__
   for word in ('ts[t] = step(a); actions[t] = a', 'embedding_select', 'index_embedding', 'stream 2', 'rollout(actions)', 'policy_index',
                'cached per T', 'epsilon', 'explore_seed', '4-byte', 'rollout_policy', 'C + 2', 'H + 1', '1 <= H <= 64'):
@@ -283,11 +290,12 @@ def test_signatures_docstrings_and_families():
   doc = base.Environment.evaluate_embedding.__doc__
   for word in ('rollout_embedding', 'PolicyEvaluation', 'evaluate_policy', 'float64'):
     assert word in doc, word
-  assert deep_sea.DeepSea._embedding_rollout_abi == ROLLOUT['deep_sea'] and catch.Catch._embedding_rollout_abi == ROLLOUT['catch']   # pylint: disable=protected-access
-  assert deep_sea.DeepSea._embedding_eval_abi == EVALUATE['deep_sea'] and catch.Catch._embedding_eval_abi == EVALUATE['catch']       # pylint: disable=protected-access
-  assert base.Environment._embedding_rollout_abi is None and cartpole.Cartpole._embedding_eval_abi is None                           # pylint: disable=protected-access
-  assert '_policy_rollout_out[T]' in inspect.getsource(base.Environment.rollout_embedding)
-  assert '_policy_evaluation_out()' in inspect.getsource(base.Environment.evaluate_embedding)
+  abi = lambda cls, name: cls._closed_loop_abi(object.__new__(cls), name)                             # pylint: disable=protected-access
+  for fam, cls in (('deep_sea', deep_sea.DeepSea), ('catch', catch.Catch)):
+    assert abi(cls, 'rollout_embedding') == ROLLOUT[fam] and abi(cls, 'evaluate_embedding') == EVALUATE[fam]
+    assert ROLLOUT[fam] in _native.EXPORTED and EVALUATE[fam] in _native.EXPORTED
+  for name in CALLS:
+    assert abi(base.Environment, name) is None and abi(cartpole.Cartpole, name) is None
 
 
 @pytest.mark.parametrize('name', CALLS)
@@ -334,7 +342,6 @@ def test_the_wrappers_refuse_instead_of_delegating(name):
 
 @pytest.mark.parametrize('name', CALLS)
 def test_arguments_are_checked_before_any_gpu_use(name):
-  abi = '_embedding_rollout_abi' if name == 'rollout_embedding' else '_embedding_eval_abi'
   for env in _envs():
     env._device = torch.device('cpu')       # the checks themselves, on host tensors: dtype, shape, contiguity
     C, A = int(np.prod(env.board_shape)), env.action_spec().num_values
@@ -358,7 +365,7 @@ def test_arguments_are_checked_before_any_gpu_use(name):
     _refused(env, name, w1=torch.zeros((0, C + 2, H)), w2=torch.zeros((0, A, H + 1)), match=msg)
     _refused(env, name, w1=pop1, w2=torch.zeros((3, A, H + 1)), match=msg)                                 # two populations of different sizes
     for h in (1, 64):
-      assert env._check_embedding(torch.zeros((C + 2, h)), torch.zeros((A, h + 1)), 4, None, 0.0, 0, name, abi) == (1, h)   # pylint: disable=protected-access
+      assert env._check_embedding(torch.zeros((C + 2, h)), torch.zeros((A, h + 1)), 4, None, 0.0, 0, name) == (1, h)   # pylint: disable=protected-access
     assert '1 <= H <= 64' in str(pytest.raises(ValueError, getattr(env, name), None, None, 4).value)
     _refused(env, name, policy_index=idx, match='must be None')
     _refused(env, name, w1=ok1.reshape(1, C + 2, H), w2=ok2.reshape(1, A, H + 1), policy_index=idx, match='must be None')   # [1, ...] is one pair
@@ -380,8 +387,8 @@ def test_arguments_are_checked_before_any_gpu_use(name):
     v1 = torch.zeros((C + 2) * H + 1)[1:].reshape(C + 2, H)
     v2 = torch.zeros(A * (H + 1) + 1)[1:].reshape(A, H + 1)
     assert v1.is_contiguous() and v1.data_ptr() % 8 == 4 and v2.data_ptr() % 8 == 4
-    assert env._check_embedding(v1, v2, 4, None, 1.0, (1 << 64) - 1, name, abi) == (1, H)                  # pylint: disable=protected-access
-    assert env._check_embedding(pop1, pop2, np.int64(7), idx, np.float32(0.5), np.int64(5), name, abi) == (4, H)   # pylint: disable=protected-access
+    assert env._check_embedding(v1, v2, 4, None, 1.0, (1 << 64) - 1, name) == (1, H)                  # pylint: disable=protected-access
+    assert env._check_embedding(pop1, pop2, np.int64(7), idx, np.float32(0.5), np.int64(5), name) == (4, H)   # pylint: disable=protected-access
     assert not env._allocated                                                                              # pylint: disable=protected-access
   # host matrices for an environment on the GPU
   env = catch.Catch(seed=0, batch=4, observation_mode='index')

@@ -240,14 +240,25 @@ def test_signatures_docstrings_and_families():
     assert list(p) == ['self', 'w1', 'w2', 'num_steps', 'policy_index', 'temperature', 'sample_seed']
     assert [p[k].kind for k in ('policy_index', 'temperature', 'sample_seed')] == [inspect.Parameter.KEYWORD_ONLY] * 3
     assert p['policy_index'].default is None and p['temperature'].default == 1.0 and p['sample_seed'].default == 0
-    src = inspect.getsource(fn)
-    assert src.index('_check_sample_embedding(') < src.index('_ensure_allocated()')                   # every refusal first
-  # the order: the environment, the matrices and the population rule (_check_embedding's, in its order), then temperature and seed
-  chk = inspect.getsource(base.Environment._check_sample_embedding)                                   # pylint: disable=protected-access
-  assert chk.index('self._check_embedding(') < chk.index('self._check_sample(')
-  inner = inspect.getsource(base.Environment._check_embedding)                                        # pylint: disable=protected-access
-  assert inner.index('_check_policy_env(') < inner.index('w1 and w2 must be') < inner.index('_check_policy_population(')
-  assert 'self._check_sample(what, temperature, sample_seed)' in inspect.getsource(base.Environment._check_sample_policy)   # pylint: disable=protected-access
+    for env in _envs():                                                                               # every refusal first: the last
+      env._device = torch.device('cpu')                                                               # one of the call allocates nothing
+      _refused(env, name, sample_seed=-1, match='sample_seed must be')
+      # the order, two faults at a time: the environment, the matrices, the population rule (rollout_embedding's, in its
+      # order), then the temperature and the seed, in sample_policy's words
+      idx = torch.zeros(4, dtype=torch.int32)
+      _refused(env, name, w1=None, num_steps=0, match='num_steps')
+      _refused(env, name, w1=None, policy_index=idx, match='w1 and w2 must be')
+      _refused(env, name, policy_index=idx, temperature=0.0, match='must be None')
+      _refused(env, name, temperature=0.0, sample_seed=-1, match='temperature must be')
+      env._logging = dict(steps=None)
+      _refused(env, name, w1=None, num_steps=0, match='Logging')
+  for tab, emb in (('sample_policy', 'sample_embedding'), ('evaluate_sampled_policy', 'evaluate_sampled_embedding')):
+    env = _envs()[1]
+    env._device = torch.device('cpu')
+    said = []
+    for call, args in ((tab, (torch.zeros((env.policy_num_states, 3)),)), (emb, _weights(env))):
+      said.append(str(pytest.raises(ValueError, getattr(env, call), *args, 4, temperature=0.0).value).replace(call, ''))
+    assert said[0] == said[1]                                                                         # one rule for the temperature
   doc = base.Environment.sample_embedding.__doc__
   for word in ('ts[t] = step(a); actions[t] = a', 'gumbel_select', 'embedding_logits', 'stream 3', 'rollout(actions)', 'policy_index',
                'cached per T', 'temperature', 'sample_seed', '4-byte', 'rollout_policy', 'rollout_embedding', 'C + 2', 'H + 1',
@@ -256,12 +267,12 @@ def test_signatures_docstrings_and_families():
   doc = base.Environment.evaluate_sampled_embedding.__doc__
   for word in ('sample_embedding', 'PolicyEvaluation', 'evaluate_policy', 'float64'):
     assert word in doc, word
-  assert deep_sea.DeepSea._embedding_sample_abi == SAMPLE['deep_sea'] and catch.Catch._embedding_sample_abi == SAMPLE['catch']   # pylint: disable=protected-access
-  assert deep_sea.DeepSea._embedding_sample_eval_abi == EVALUATE['deep_sea']                          # pylint: disable=protected-access
-  assert catch.Catch._embedding_sample_eval_abi == EVALUATE['catch']                                  # pylint: disable=protected-access
-  assert base.Environment._embedding_sample_abi is None and cartpole.Cartpole._embedding_sample_eval_abi is None   # pylint: disable=protected-access
-  assert '_policy_rollout_out[T]' in inspect.getsource(base.Environment.sample_embedding)
-  assert '_policy_evaluation_out()' in inspect.getsource(base.Environment.evaluate_sampled_embedding)
+  abi = lambda cls, name: cls._closed_loop_abi(object.__new__(cls), name)                             # pylint: disable=protected-access
+  for fam, cls in (('deep_sea', deep_sea.DeepSea), ('catch', catch.Catch)):
+    assert abi(cls, 'sample_embedding') == SAMPLE[fam] and abi(cls, 'evaluate_sampled_embedding') == EVALUATE[fam]
+    assert SAMPLE[fam] in _native.EXPORTED and EVALUATE[fam] in _native.EXPORTED
+  for name in CALLS:
+    assert abi(base.Environment, name) is None and abi(cartpole.Cartpole, name) is None
 
 
 @pytest.mark.parametrize('name', CALLS)
@@ -308,7 +319,6 @@ def test_the_wrappers_refuse_instead_of_delegating(name):
 
 @pytest.mark.parametrize('name', CALLS)
 def test_arguments_are_checked_before_any_gpu_use(name):
-  abi = '_embedding_sample_abi' if name == 'sample_embedding' else '_embedding_sample_eval_abi'
   for env in _envs():
     env._device = torch.device('cpu')       # the checks themselves, on host tensors: dtype, shape, contiguity
     C, A = int(np.prod(env.board_shape)), env.action_spec().num_values
@@ -332,7 +342,7 @@ def test_arguments_are_checked_before_any_gpu_use(name):
     _refused(env, name, w1=torch.zeros((0, C + 2, H)), w2=torch.zeros((0, A, H + 1)), match=msg)
     _refused(env, name, w1=pop1, w2=torch.zeros((3, A, H + 1)), match=msg)                                 # two populations of different sizes
     for h in (1, 64):
-      assert env._check_sample_embedding(torch.zeros((C + 2, h)), torch.zeros((A, h + 1)), 4, None, 1.0, 0, name, abi) == (1, h, 1.0)   # pylint: disable=protected-access
+      assert env._check_sample_embedding(torch.zeros((C + 2, h)), torch.zeros((A, h + 1)), 4, None, 1.0, 0, name) == (1, h, 1.0)   # pylint: disable=protected-access
     assert '1 <= H <= 64' in str(pytest.raises(ValueError, getattr(env, name), None, None, 4).value)
     _refused(env, name, policy_index=idx, match='must be None')
     _refused(env, name, w1=ok1.reshape(1, C + 2, H), w2=ok2.reshape(1, A, H + 1), policy_index=idx, match='must be None')   # [1, ...] is one pair
@@ -356,8 +366,8 @@ def test_arguments_are_checked_before_any_gpu_use(name):
     v1 = torch.zeros((C + 2) * H + 1)[1:].reshape(C + 2, H)
     v2 = torch.zeros(A * (H + 1) + 1)[1:].reshape(A, H + 1)
     assert v1.is_contiguous() and v1.data_ptr() % 8 == 4 and v2.data_ptr() % 8 == 4
-    assert env._check_sample_embedding(v1, v2, 4, None, 0.25, (1 << 64) - 1, name, abi) == (1, H, 4.0)     # pylint: disable=protected-access
-    assert env._check_sample_embedding(pop1, pop2, np.int64(7), idx, np.float32(4.0), np.int64(5), name, abi) == (4, H, 0.25)   # pylint: disable=protected-access
+    assert env._check_sample_embedding(v1, v2, 4, None, 0.25, (1 << 64) - 1, name) == (1, H, 4.0)     # pylint: disable=protected-access
+    assert env._check_sample_embedding(pop1, pop2, np.int64(7), idx, np.float32(4.0), np.int64(5), name) == (4, H, 0.25)   # pylint: disable=protected-access
     assert not env._allocated                                                                              # pylint: disable=protected-access
   # host matrices for an environment on the GPU
   env = catch.Catch(seed=0, batch=4, observation_mode='index')

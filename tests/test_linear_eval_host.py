@@ -204,8 +204,9 @@ def test_signature_and_result_type():
   assert all(p[k].default is inspect.Parameter.empty for k in ('weights', 'observation', 'num_steps'))     # the observation is required
   assert base.LinearEvaluation._fields == ('episodes', 'return_sum', 'episode_return_sum', 'observation')
   assert base.PolicyEvaluation._fields == ('episodes', 'return_sum', 'episode_return_sum')
-  assert cartpole.Cartpole._linear_eval_abi == cartpole.CartpoleSwingup._linear_eval_abi == ENTRY['cartpole']    # pylint: disable=protected-access
-  assert mountain_car.MountainCar._linear_eval_abi == ENTRY['mountain_car']                                      # pylint: disable=protected-access
+  abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), 'evaluate_linear')                                 # pylint: disable=protected-access
+  assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole'] and abi(mountain_car.MountainCar) == ENTRY['mountain_car']
+  assert abi(base.Environment) is None and abi(catch.Catch) is None and set(ENTRY.values()) <= set(_native.EXPORTED)
   assert [_dim(e) for e in _envs()] == [DIMS['cartpole'], DIMS['swingup'], DIMS['mountain_car']]
   doc = base.Environment.evaluate_linear.__doc__
   assert 'linear_select' in doc and 'never reads its row' in doc

@@ -274,18 +274,39 @@ def test_signatures_docstrings_and_families():
     for word in ('mlp2_select(w1[row], w2[row], w3[row], obs)', 'torch.cat([lin.weight, lin.bias[:, None]], 1)', 'torch.nn.Linear',
                  'policy_index', '1 <= H1, H2 <= 64', sibling):
       assert word in fn.__doc__, (call, word)
-    attr = '_mlp2_eval_abi' if call == 'evaluate' else '_mlp2_rollout_abi'
-    assert getattr(cartpole.Cartpole, attr) == getattr(cartpole.CartpoleSwingup, attr) == ENTRY['cartpole', call]
-    assert getattr(mountain_car.MountainCar, attr) == ENTRY['mountain_car', call]
-    assert getattr(base.Environment, attr) is None and getattr(catch.Catch, attr) is None
-    src = inspect.getsource(fn)
-    assert 'self._check_evaluate_mlp2(' in src and src.index('_check_evaluate_mlp2(') < src.index('_ensure_allocated()')
-  roll = inspect.getsource(base.Environment.rollout_mlp2)
-  assert roll.index('_check_evaluate_mlp2(') < roll.index('_check_trajectory_slab(') < roll.index('_ensure_allocated()')
-  assert '_trajectory_out(T)' in roll and '_fused_eval_out()' in inspect.getsource(base.Environment.evaluate_mlp2)
-  check = inspect.getsource(base.Environment._check_evaluate_mlp2)         # pylint: disable=protected-access
-  for helper in ('self._check_fused_eval(', 'self._is_eval_weight(', 'self._check_fused_eval_rows('):
-    assert helper in check, helper
+    abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), f'{call}_mlp2')        # pylint: disable=protected-access,cell-var-from-loop
+    assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole', call]
+    assert abi(mountain_car.MountainCar) == ENTRY['mountain_car', call] and ENTRY['cartpole', call] in _native.EXPORTED
+    assert abi(base.Environment) is None and abi(catch.Catch) is None and ENTRY['mountain_car', call] in _native.EXPORTED
+    for env in _envs():
+      D = _dim(env)
+      env._device = torch.device('cpu')
+      good = dict(w1=torch.zeros((5, D + 1)), w2=torch.zeros((4, 6)), w3=torch.zeros((3, 5)), observation=torch.zeros((4, D)))
+      # every refusal first: the last one of the arguments allocates nothing; and the order, two faults at a time
+      _refused(env, call, match='must be None', policy_index=torch.zeros(4, dtype=torch.int32), **good)
+      _refused(env, call, match='w3 must be', policy_index=torch.zeros(4, dtype=torch.int32), **dict(good, w3=None))
+      _refused(env, call, match='observation must be', policy_index=torch.zeros(4, dtype=torch.int32), **dict(good, observation=None))
+      # the refusals the three forms share are said in evaluate_mlp's words: the environment, the scalars, the rows, the population
+      for kw in (dict(num_steps=0), dict(epsilon=2.0), dict(explore_seed=-1), dict(observation=None),
+                 dict(policy_index=torch.zeros(4, dtype=torch.int32))):
+        said = []
+        for name, w in ((f'{call}_mlp2', (good['w1'], good['w2'], good['w3'])), (f'{call}_mlp', (good['w1'], torch.zeros((3, 6))))):
+          args = {'observation': good['observation'], **kw}
+          with pytest.raises(ValueError) as info:
+            getattr(env, name)(*w, args.pop('observation'), args.pop('num_steps', 4), **args)
+          said.append(str(info.value).replace(name, '').replace('triple', 'pair'))
+        assert said[0] == said[1], kw
+      # the slab comes after the arguments, for the recording call alone; the returns-only call goes on to allocate (never on 'meta')
+      env._device = torch.device('meta')
+      env._batch = -(-(1 << 32) // (4 * D))
+      big = dict({k: torch.zeros(v.shape, device='meta') for k, v in good.items()}, observation=torch.zeros((env._batch, D), device='meta'))
+      if call == 'rollout':
+        _refused(env, call, match='must be None', policy_index=torch.zeros(env._batch, dtype=torch.int32, device='meta'), **big)
+        _refused(env, call, match='4 GiB', **big)
+      else:
+        with pytest.raises(RuntimeError, match='no HIP device'):
+          env.evaluate_mlp2(*big.values(), 4)
+        assert not env._allocated and env._linear_eval_out is None and not env._policy_rollout_out
   assert list(inspect.signature(observations.mlp2_logits).parameters) == ['w1', 'w2', 'w3', 'obs']
   assert list(inspect.signature(observations.mlp2_select).parameters) == ['w1', 'w2', 'w3', 'obs', 'return_preactivations']
   assert 'torch.cat([lin.weight, lin.bias[:, None]], 1)' in observations.mlp2_logits.__doc__
@@ -313,8 +334,8 @@ def test_a_slab_of_4_gib_is_refused_by_the_recording_call_alone(trap):
     env._device = torch.device('cpu')
     env._batch = 4
     ok = dict(w1=torch.zeros((5, D + 1)), observation=torch.zeros((4, D)))
-    env._check_evaluate_mlp2(ok['w1'], torch.zeros((4, 6)), torch.zeros((3, 5)), ok['observation'], 4, None, 0.0, 0, what='rollout_mlp2',
-                             abi='_mlp2_rollout_abi')                     # pylint: disable=protected-access
+    env._check_evaluate_mlp2(ok['w1'], torch.zeros((4, 6)), torch.zeros((3, 5)), ok['observation'], 4, None, 0.0, 0,
+                             what='rollout_mlp2')                         # pylint: disable=protected-access
     env._batch = -(-(1 << 32) // (4 * D))                                  # the first batch whose [B, D] slab reaches 4 GiB
     with pytest.raises(ValueError, match='rollout_mlp2: .* 4 GiB'):
       env._check_trajectory_slab('rollout_mlp2')                           # pylint: disable=protected-access
@@ -322,8 +343,13 @@ def test_a_slab_of_4_gib_is_refused_by_the_recording_call_alone(trap):
     big = torch.zeros((1, D)).expand(env._batch, D)                        # (not contiguous: refused first, as an argument)
     with pytest.raises(ValueError, match='rollout_mlp2: observation must be'):
       env.rollout_mlp2(ok['w1'], torch.zeros((4, 6)), torch.zeros((3, 5)), big, 4)
-    src = inspect.getsource(base.Environment.evaluate_mlp2)
-    assert '_check_trajectory_slab' not in src                             # evaluate mode writes no slab
+    meta = [torch.zeros(shape, device='meta') for shape in ((5, D + 1), (4, 6), (3, 5), (env._batch, D))]
+    env._device = torch.device('meta')
+    with pytest.raises(ValueError, match='rollout_mlp2: .* 4 GiB'):
+      env.rollout_mlp2(*meta, 4)
+    with pytest.raises(RuntimeError, match='no HIP device'):               # evaluate mode writes no slab: it goes on to allocate
+      env.evaluate_mlp2(*meta, 4)                                          # (never on 'meta')
+    env._device = torch.device('cpu')
     env._batch -= 1
     env._check_trajectory_slab('rollout_mlp2')                             # pylint: disable=protected-access
     assert not env._allocated                                              # pylint: disable=protected-access

@@ -27,7 +27,6 @@ HEADER = os.path.join(ROOT, 'include', 'bsuite_amd.h')
 SHIM = os.path.join(ROOT, 'tests', 'csrc', 'mlp2_sample_shim.c')
 CALLS = ('sample_mlp2', 'evaluate_sampled_mlp2')
 SUFFIX = dict(sample_mlp2='mlp2_sample', evaluate_sampled_mlp2='mlp2_sample_evaluate')
-ABI_ATTR = dict(sample_mlp2='_mlp2_sample_abi', evaluate_sampled_mlp2='_mlp2_sample_eval_abi')
 ENTRY = {(fam, c): f'bsx_{fam}_{SUFFIX[c]}' for fam in ('cartpole', 'mountain_car') for c in CALLS}
 DIMS = [3, 6, 8]
 WIDTHS = [(1, 1), (33, 7), (7, 17), (64, 64)]
@@ -211,6 +210,22 @@ def _refused(env, name, exc=ValueError, match=None, **kw):
   assert not raw._allocated and not raw._policy_rollout_out and raw._linear_eval_out is None      # pylint: disable=protected-access
 
 
+def _native_arguments(env, name, *args, **kw):
+  """What env.<name>(...) hands to the library — (entry point, arguments, T) — with the allocation and the launch replaced on
+  this instance and its columns on the CPU."""
+  seen = []
+  env._device = torch.device('cpu')
+  env._ensure_allocated = lambda: None
+  env._call_desc = _native.Call()
+  env._state = dict(state=torch.zeros((4, 4)), steps=torch.zeros(4, dtype=torch.int32))
+  env._info = torch.zeros((1, 4), dtype=torch.float64)
+  env._launch_steps = lambda fn, a, T, what: seen.append((fn.__name__, a, T, what))
+  out = getattr(env, name)(*args, **kw)
+  (entry, a, T, what), = seen
+  assert what == name
+  return entry, a, T, out
+
+
 def test_signatures_docstrings_and_families():
   want = ['self', 'w1', 'w2', 'w3', 'observation', 'num_steps', 'policy_index', 'temperature', 'sample_seed']
   for name, sibling, greedy in (('sample_mlp2', 'sample_mlp', 'rollout_mlp2'), ('evaluate_sampled_mlp2', 'evaluate_sampled_mlp', 'evaluate_mlp2')):
@@ -225,19 +240,35 @@ def test_signatures_docstrings_and_families():
                  'torch.cat([lin.weight, lin.bias[:, None]], 1)', 'torch.nn.Linear', 'policy_index', '1 <= H1, H2 <= 64', sibling,
                  'a = 0 where the lane resets on this call'):
       assert word in fn.__doc__, (name, word)
-    attr = ABI_ATTR[name]
-    assert getattr(cartpole.Cartpole, attr) == getattr(cartpole.CartpoleSwingup, attr) == ENTRY['cartpole', name]
-    assert getattr(mountain_car.MountainCar, attr) == ENTRY['mountain_car', name]
-    assert getattr(base.Environment, attr) is None and getattr(catch.Catch, attr) is None
-    src = inspect.getsource(fn)
-    assert 'self._check_evaluate_mlp2(' in src and 'self._check_sample(' in src and 'self._mlp2_struct(' in src
-    assert src.index('_check_evaluate_mlp2(') < src.index('_check_sample(') < src.index('_ensure_allocated()')
-    assert 'int(sample_seed)' in src and 'epsilon' not in inspect.signature(fn).parameters
-  rec = inspect.getsource(base.Environment.sample_mlp2)
-  assert rec.index('_check_sample(') < rec.index('_check_trajectory_slab(') < rec.index('_ensure_allocated()')
-  assert '_trajectory_out(T)' in rec
-  ev = inspect.getsource(base.Environment.evaluate_sampled_mlp2)
-  assert '_fused_eval_out()' in ev and '_check_trajectory_slab' not in ev   # returns only: no slab is written
+    abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), name)      # pylint: disable=protected-access,cell-var-from-loop
+    assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole', name]
+    assert abi(mountain_car.MountainCar) == ENTRY['mountain_car', name] and ENTRY['cartpole', name] in _native.EXPORTED
+    assert abi(base.Environment) is None and abi(catch.Catch) is None and ENTRY['mountain_car', name] in _native.EXPORTED
+    assert 'epsilon' not in inspect.signature(fn).parameters
+    for env in _envs():
+      # the refusals are the greedy call's, then the temperature and the seed — two faults at a time, the earlier one's message
+      # — and the last of them allocates nothing
+      D = _dim(env)
+      env._device = torch.device('cpu')
+      good = dict(w1=torch.zeros((5, D + 1)), w2=torch.zeros((4, 6)), w3=torch.zeros((3, 5)), observation=torch.zeros((4, D)))
+      _refused(env, name, match='w3 must be', temperature=0.0, **dict(good, w3=None))
+      _refused(env, name, match='temperature must be', temperature=0.0, sample_seed=-1, **good)
+      _refused(env, name, match='sample_seed must be', sample_seed=-1, **good)
+      # what reaches the library: the triple in one bsx_mlp2_t with epsilon 0.0 and the SAMPLE seed in its explore_seed field,
+      # 1 / temperature after it, the two state columns, the outputs — the recording call's with the action column — and info
+      entry, a, T, out = _native_arguments(env, name, *good.values(), 7, temperature=4.0, sample_seed=(1 << 64) - 3)
+      pol = a[2]._obj                                                      # pylint: disable=protected-access
+      assert entry == ENTRY['mountain_car' if D == 3 else 'cartpole', name] and T == 7 and isinstance(pol, _native.Mlp2)
+      assert (pol.w1, pol.w2, pol.w3, pol.observation_in) == tuple(t.data_ptr() for t in good.values())
+      assert (pol.hidden1, pol.hidden2, pol.n_policies, pol.policy_index, pol.epsilon, pol.explore_seed) == (5, 4, 1, None, 0.0, (1 << 64) - 3)
+      assert a[3] == 0.25 and a[4:6] == tuple(t.data_ptr() for t in env._state.values()) and a[-1] == env._info.data_ptr()
+      if name == 'sample_mlp2':                                            # the [T,B] buffers of the rollout_* calls, + the actions
+        ts, actions = out
+        assert len(a) == 9 and isinstance(a[6], _native.TimeStepPtrs) and a[6].reward == ts.reward.data_ptr() and a[7] == actions.data_ptr()
+        assert env._policy_rollout_out[7][2] is ts and env._policy_rollout_out[7][3] is actions and env._linear_eval_out is None
+      else:                                                                # evaluate_linear's result columns; no [T,B] buffer
+        assert len(a) == 8 and isinstance(a[6], _native.LinearEvalPtrs) and out is env._linear_eval_out and not env._policy_rollout_out
+        assert (a[6].episodes, a[6].return_sum, a[6].episode_return_sum, a[6].observation_out) == tuple(t.data_ptr() for t in out)
   for word in ('-inf logit masks', 'NaN score never wins', 'never reads its row'):
     assert word in base.Environment.sample_mlp2.__doc__, word
   assert 'invalid_action_count()' in base.Environment.evaluate_sampled_mlp2.__doc__
@@ -283,7 +314,16 @@ def test_a_slab_of_4_gib_is_refused_by_the_recording_call_alone(trap):
     env._batch -= 1
     env._check_trajectory_slab('sample_mlp2')                              # pylint: disable=protected-access
     assert not env._allocated                                              # pylint: disable=protected-access
-  assert '_check_trajectory_slab' not in inspect.getsource(base.Environment.evaluate_sampled_mlp2)
+  for env in _envs():                                                      # returns only: no slab is written, none is refused —
+    D = _dim(env)                                                          # the call goes on to allocate (never on 'meta')
+    env._device = torch.device('meta')
+    env._batch = -(-(1 << 32) // (4 * D))
+    w = [torch.zeros(shape, device='meta') for shape in ((5, D + 1), (4, 6), (3, 5), (env._batch, D))]
+    with pytest.raises(RuntimeError, match='no HIP device'):
+      env.evaluate_sampled_mlp2(*w, 4)
+    with pytest.raises(ValueError, match='sample_mlp2: .* 4 GiB'):
+      env.sample_mlp2(*w, 4)
+    assert not env._allocated and env._linear_eval_out is None             # pylint: disable=protected-access
 
 
 @pytest.mark.parametrize('name', CALLS)

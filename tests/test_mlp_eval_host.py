@@ -306,15 +306,32 @@ def test_signature_result_type_and_families():
   assert [p[k].kind for k in ('policy_index', 'epsilon', 'explore_seed')] == [inspect.Parameter.KEYWORD_ONLY] * 3
   assert p['policy_index'].default is None and p['epsilon'].default == 0.0 and p['explore_seed'].default == 0
   assert all(p[k].default is inspect.Parameter.empty for k in ('w1', 'w2', 'observation', 'num_steps'))
-  assert cartpole.Cartpole._mlp_eval_abi == cartpole.CartpoleSwingup._mlp_eval_abi == ENTRY['cartpole']     # pylint: disable=protected-access
-  assert mountain_car.MountainCar._mlp_eval_abi == ENTRY['mountain_car']                                    # pylint: disable=protected-access
-  assert base.Environment._mlp_eval_abi is None                                                             # pylint: disable=protected-access
+  abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), 'evaluate_mlp')                               # pylint: disable=protected-access
+  assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole'] and abi(mountain_car.MountainCar) == ENTRY['mountain_car']
+  assert abi(base.Environment) is None and abi(catch.Catch) is None and set(ENTRY.values()) <= set(_native.EXPORTED)
   assert base.LinearEvaluation._fields == ('episodes', 'return_sum', 'episode_return_sum', 'observation')
   doc = base.Environment.evaluate_mlp.__doc__
   assert 'mlp_select' in doc and 'LinearEvaluation' in doc and 'policy_index' in doc
-  # the two checks share their common part instead of repeating it
-  assert '_check_fused_eval(' in inspect.getsource(base.Environment._check_evaluate_mlp)                     # pylint: disable=protected-access
-  assert '_check_fused_eval(' in inspect.getsource(base.Environment._check_evaluate_linear)                  # pylint: disable=protected-access
+  # the two calls share their common refusals: the same words for the environment, num_steps, epsilon and the seed
+  def spoil(what):
+    env = mountain_car.MountainCar(seed=0, batch=4, rng='mt19937' if what == 'rng' else 'philox')
+    env._device = torch.device('cpu')                                                                       # pylint: disable=protected-access
+    if what == 'logging':
+      env._logging = dict(steps=None)                                                                       # pylint: disable=protected-access
+    if what == 'grouped':
+      env._grouped_by = object()                                                                            # pylint: disable=protected-access
+    if what == 'wrapped':
+      wrappers.RewardScale(env, reward_scale=2.0)
+    return env, dict(dict(num_steps=dict(num_steps=0), epsilon=dict(epsilon=2.0), seed=dict(explore_seed=-1)).get(what, {}))
+  for what in ('rng', 'logging', 'grouped', 'wrapped', 'num_steps', 'epsilon', 'seed'):
+    said = []
+    for call, weights in (('evaluate_linear', (torch.zeros((3, 4)),)), ('evaluate_mlp', (torch.zeros((5, 4)), torch.zeros((3, 6))))):
+      env, kw = spoil(what)
+      with pytest.raises((ValueError, RuntimeError)) as info:
+        getattr(env, call)(*weights, torch.zeros((4, 3)), kw.pop('num_steps', 4), **kw)
+      said.append(str(info.value).replace(call, ''))
+      assert not env._allocated and env._linear_eval_out is None                                            # pylint: disable=protected-access
+    assert said[0] == said[1], what
 
 
 def test_views_families_and_modes_are_refused():

@@ -18,7 +18,7 @@ import torch
 
 import bsuite_amd
 from bsuite_amd import _native
-from bsuite_amd.environments import base, catch, deep_sea
+from bsuite_amd.environments import base, cartpole, catch, deep_sea
 from bsuite_amd.utils import wrappers
 from tests import policy_eval_util as pe
 
@@ -164,7 +164,9 @@ def test_signature_and_result_type():
   assert [p[k].kind for k in ('policy_index', 'epsilon', 'explore_seed')] == [inspect.Parameter.KEYWORD_ONLY] * 3
   assert p['policy_index'].default is None and p['epsilon'].default == 0.0 and p['explore_seed'].default == 0
   assert base.PolicyEvaluation._fields == ('episodes', 'return_sum', 'episode_return_sum')
-  assert catch.Catch._policy_eval_abi == ENTRY['catch'] and deep_sea.DeepSea._policy_eval_abi == ENTRY['deep_sea']    # pylint: disable=protected-access
+  abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), 'evaluate_policy')                                      # pylint: disable=protected-access
+  assert abi(catch.Catch) == ENTRY['catch'] and abi(deep_sea.DeepSea) == ENTRY['deep_sea']
+  assert abi(base.Environment) is None and abi(cartpole.Cartpole) is None and set(ENTRY.values()) <= set(_native.EXPORTED)
   doc = base.Environment.evaluate_policy.__doc__
   assert 'already running' in doc and 'index_add_' in doc              # the partial first episode; reducing by policy
 

@@ -455,14 +455,24 @@ def test_signatures_docstrings_and_families():
     for word in ('actions', 'ts[t] = step(a); actions[t] = a', f'rollout_{kind}', f'{kind}_logits', 'gumbel_select', 'rollout(actions)',
                  'policy_index', 'cached per T', 'temperature', 'sample_seed', 'stream 3' if kind == 'linear' else 'sample_linear'):
       assert word in fn.__doc__, (kind, word)
-    attr = f'_{kind}_sample_abi'
-    assert getattr(cartpole.Cartpole, attr) == getattr(cartpole.CartpoleSwingup, attr) == ENTRY['cartpole', kind]
-    assert getattr(mountain_car.MountainCar, attr) == ENTRY['mountain_car', kind]
-    assert getattr(base.Environment, attr) is None and getattr(catch.Catch, attr) is None
-    # the refusals are the recording call's, through its check functions, then the two of its own — all before the allocation
-    src = inspect.getsource(fn)
-    assert src.index(f'_check_evaluate_{kind}(') < src.index('_check_sample(') < src.index('_check_trajectory_slab(') < src.index('_ensure_allocated()')
-    assert '_trajectory_out(T)' in src                                     # rollout_*'s buffers
+    abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), f'sample_{kind}')       # pylint: disable=protected-access,cell-var-from-loop
+    assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole', kind]
+    assert abi(mountain_car.MountainCar) == ENTRY['mountain_car', kind] and ENTRY['cartpole', kind] in _native.EXPORTED
+    assert abi(base.Environment) is None and abi(catch.Catch) is None and ENTRY['mountain_car', kind] in _native.EXPORTED
+    # the refusals are the recording call's, then the two of its own, then the slab — two faults at a time, the earlier one's
+    # message — all before the allocation
+    for env in _envs():
+      D, first = _dim(env), 'weights' if kind == 'linear' else 'w1'
+      shapes = dict(weights=(3, D + 1)) if kind == 'linear' else dict(w1=(5, D + 1), w2=(3, 6))
+      env._device = torch.device('cpu')
+      good = dict({k: torch.zeros(v) for k, v in shapes.items()}, observation=torch.zeros((4, D)))
+      _refused(env, kind, match=f'{first} must be', temperature=0.0, **dict(good, **{first: None}))
+      _refused(env, kind, match='temperature must be', temperature=0.0, sample_seed=-1, **good)
+      env._device = torch.device('meta')                                   # tensors without storage: a slab of 4 GiB passes the
+      env._batch = -(-(1 << 32) // (4 * D))                                # arguments' checks
+      big = dict({k: torch.zeros(v, device='meta') for k, v in shapes.items()}, observation=torch.zeros((env._batch, D), device='meta'))
+      _refused(env, kind, match='sample_seed must be', sample_seed=-1, **big)
+      _refused(env, kind, match='4 GiB', **big)
   for name in ('linear_logits', 'mlp_logits', 'gumbel_select'):
     src = inspect.getsource(getattr(observations, name))
     code = re.sub(r'""".*?"""', '', src, flags=re.S)

@@ -238,15 +238,26 @@ def test_signatures_docstrings_and_families():
     for word in (f'sample_{kind}', 'LinearEvaluation', 'evaluate_linear', 'no TimeStep is written', 'ts = step(a); obs = ts.observation', f'{kind}_logits', 'gumbel_select', 'policy_index', 'temperature',
                  'sample_seed', 'overwritten by the next call', 'bit for bit'):
       assert word in doc, (kind, word)
-    attr = f'_{kind}_sample_eval_abi'
-    assert getattr(cartpole.Cartpole, attr) == getattr(cartpole.CartpoleSwingup, attr) == ENTRY['cartpole', kind]
-    assert getattr(mountain_car.MountainCar, attr) == ENTRY['mountain_car', kind]
-    assert getattr(base.Environment, attr) is None and getattr(catch.Catch, attr) is None
-    # the refusals are sample_*'s, through its check functions, without the slab — all before the allocation
-    src = inspect.getsource(fn)
-    assert src.index(f'_check_evaluate_{kind}(') < src.index('_check_sample(') < src.index('_ensure_allocated()')
-    assert '_check_trajectory_slab' not in src and '_trajectory_out' not in src
-    assert '_fused_eval_out()' in src                                      # evaluate_linear's buffers
+    abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), f'evaluate_sampled_{kind}')   # pylint: disable=protected-access,cell-var-from-loop
+    assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole', kind]
+    assert abi(mountain_car.MountainCar) == ENTRY['mountain_car', kind] and ENTRY['cartpole', kind] in _native.EXPORTED
+    assert abi(base.Environment) is None and abi(catch.Catch) is None and ENTRY['mountain_car', kind] in _native.EXPORTED
+    # the refusals are sample_*'s, in its order — two faults at a time, the earlier one's message — without the slab, all
+    # before the allocation
+    for env in _envs():
+      D, first = _dim(env), 'weights' if kind == 'linear' else 'w1'
+      shapes = dict(weights=(3, D + 1)) if kind == 'linear' else dict(w1=(5, D + 1), w2=(3, 6))
+      env._device = torch.device('cpu')
+      good = dict({k: torch.zeros(v) for k, v in shapes.items()}, observation=torch.zeros((4, D)))
+      _refused(env, kind, match=f'{first} must be', temperature=0.0, **dict(good, **{first: None}))
+      _refused(env, kind, match='temperature must be', temperature=0.0, sample_seed=-1, **good)
+      env._device = torch.device('meta')                                   # tensors without storage: a slab of 4 GiB passes the
+      env._batch = -(-(1 << 32) // (4 * D))                                # arguments' checks
+      big = dict({k: torch.zeros(v, device='meta') for k, v in shapes.items()}, observation=torch.zeros((env._batch, D), device='meta'))
+      _refused(env, kind, match='sample_seed must be', sample_seed=-1, **big)
+      with pytest.raises(RuntimeError, match='no HIP device'):             # no slab is written, none is refused: the call goes on
+        getattr(env, f'evaluate_sampled_{kind}')(*list(big.values())[:-1], big['observation'], 4)     # to allocate (never on 'meta')
+      assert not env._allocated and env._linear_eval_out is None and not env._policy_rollout_out
 
 
 def test_views_families_and_modes_are_refused():

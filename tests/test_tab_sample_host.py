@@ -273,12 +273,32 @@ def test_signatures_docstrings_and_families():
     assert [p[k].kind for k in ('policy_index', 'temperature', 'sample_seed')] == [inspect.Parameter.KEYWORD_ONLY] * 3
     assert p['policy_index'].default is None and p['temperature'].default == 1.0 and p['sample_seed'].default == 0
     assert list(p)[3:] == list(inspect.signature(base.Environment.sample_linear).parameters)[4:]
-    src = inspect.getsource(fn)
-    assert src.index('_check_sample_policy(') < src.index('_ensure_allocated()')                      # every refusal first
-  chk = inspect.getsource(base.Environment._check_sample_policy)                                      # pylint: disable=protected-access
-  assert chk.index('_check_policy_env(') < chk.index('logits must be') < chk.index('_check_policy_population(') < chk.index('_check_sample(')
-  old = inspect.getsource(base.Environment._check_rollout_policy)                                     # pylint: disable=protected-access
-  assert '_check_policy_env(' in old and '_check_policy_population(' in old                           # the split: two parts, shared
+    for env in _envs():                                                                               # every refusal first: the last
+      env._device = torch.device('cpu')                                                               # one of the call allocates nothing
+      _refused(env, name, sample_seed=-1, match='sample_seed must be')
+      # the order, two faults at a time: the environment, the logits, the population rule, the temperature, the seed
+      idx = torch.zeros(4, dtype=torch.int32)
+      _refused(env, name, logits=None, num_steps=0, match='num_steps')
+      _refused(env, name, logits=None, policy_index=idx, match='logits must be')
+      _refused(env, name, policy_index=idx, temperature=0.0, match='must be None')
+      _refused(env, name, temperature=0.0, sample_seed=-1, match='temperature must be')
+      env._logging = dict(steps=None)
+      _refused(env, name, logits=None, num_steps=0, match='Logging')
+  # the environment's part and the population rule are rollout_policy's: the same words
+  for drawn, greedy in (('sample_policy', 'rollout_policy'), ('evaluate_sampled_policy', 'evaluate_policy')):
+    for spoil, kw in ((lambda e: setattr(e, '_grouped_by', object()), {}), (lambda e: None, dict(num_steps=0)),
+                      (lambda e: None, dict(policy_index=torch.zeros(4, dtype=torch.int32)))):
+      said = []
+      for call, table in ((drawn, _logits), (greedy, lambda e: torch.zeros(e.policy_num_states, dtype=torch.uint8))):
+        env = _envs()[1]
+        env._device = torch.device('cpu')
+        spoil(env)
+        args = dict(kw)
+        with pytest.raises((ValueError, RuntimeError)) as info:
+          getattr(env, call)(table(env), args.pop('num_steps', 4), **args)
+        said.append(str(info.value).replace(call, ''))
+        assert not env._allocated
+      assert said[0] == said[1], (drawn, kw)
   doc = base.Environment.sample_policy.__doc__
   for word in ('ts[t] = step(a); actions[t] = a', 'gumbel_select', 'policy_key', 'stream 3', 'rollout(actions)', 'policy_index',
                'cached per T', 'temperature', 'sample_seed', '4-byte', '-inf', 'rollout_policy'):
@@ -286,12 +306,12 @@ def test_signatures_docstrings_and_families():
   doc = base.Environment.evaluate_sampled_policy.__doc__
   for word in ('sample_policy', 'PolicyEvaluation', 'evaluate_policy', 'float64'):
     assert word in doc, word
-  assert deep_sea.DeepSea._policy_sample_abi == SAMPLE['deep_sea'] and catch.Catch._policy_sample_abi == SAMPLE['catch']                      # pylint: disable=protected-access
-  assert deep_sea.DeepSea._policy_sample_eval_abi == SAMPLE_EVAL['deep_sea'] and catch.Catch._policy_sample_eval_abi == SAMPLE_EVAL['catch']  # pylint: disable=protected-access
-  assert base.Environment._policy_sample_abi is None and cartpole.Cartpole._policy_sample_eval_abi is None                                     # pylint: disable=protected-access
-  assert 'sample_policy(' in inspect.getsource(base.Environment.sample_policy) and '_policy_rollout_out[T]' in inspect.getsource(base.Environment.sample_policy)
-  assert '_policy_evaluation_out()' in inspect.getsource(base.Environment.evaluate_sampled_policy)
-  assert '_policy_evaluation_out()' in inspect.getsource(base.Environment.evaluate_policy)            # the same cached columns
+  abi = lambda cls, name: cls._closed_loop_abi(object.__new__(cls), name)                             # pylint: disable=protected-access
+  for fam, cls in (('deep_sea', deep_sea.DeepSea), ('catch', catch.Catch)):
+    assert abi(cls, 'sample_policy') == SAMPLE[fam] and abi(cls, 'evaluate_sampled_policy') == SAMPLE_EVAL[fam]
+    assert SAMPLE[fam] in _native.EXPORTED and SAMPLE_EVAL[fam] in _native.EXPORTED
+  for name in CALLS:
+    assert abi(base.Environment, name) is None and abi(cartpole.Cartpole, name) is None
 
 
 @pytest.mark.parametrize('name', CALLS)
@@ -402,9 +422,9 @@ def test_arguments_are_checked_before_any_gpu_use(name):
     # a view that starts one float into a buffer passes the checks (only 4-byte alignment is assumed)
     view = torch.zeros(S * A + 1)[1:].reshape(S, A)
     assert view.is_contiguous() and view.data_ptr() % 8 == 4
-    P, beta = env._check_sample_policy(view, 4, None, 4.0, (1 << 64) - 1, name, '_policy_sample_abi')      # pylint: disable=protected-access
+    P, beta = env._check_sample_policy(view, 4, None, 4.0, (1 << 64) - 1, name)      # pylint: disable=protected-access
     assert (P, beta) == (1, 0.25)
-    assert env._check_sample_policy(pop, np.int64(7), idx, np.float32(0.5), np.int64(5), name, '_policy_sample_abi') == (4, 2.0)   # pylint: disable=protected-access
+    assert env._check_sample_policy(pop, np.int64(7), idx, np.float32(0.5), np.int64(5), name) == (4, 2.0)   # pylint: disable=protected-access
     assert not env._allocated                                                                              # pylint: disable=protected-access
   # host logits for an environment on the GPU
   env = catch.Catch(seed=0, batch=4, observation_mode='index')

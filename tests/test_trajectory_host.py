@@ -65,14 +65,27 @@ def test_signatures_docstrings_and_families():
     for word in ('actions', 'ts[t] = step(a); actions[t] = a', f'evaluate_{kind}', f'{kind}_select', 'rollout(actions)', 'policy_index',
                  'cached per T'):
       assert word in fn.__doc__, (kind, word)
-    attr = f'_{kind}_rollout_abi'
-    assert getattr(cartpole.Cartpole, attr) == getattr(cartpole.CartpoleSwingup, attr) == ENTRY['cartpole', kind]
-    assert getattr(mountain_car.MountainCar, attr) == ENTRY['mountain_car', kind]
-    assert getattr(base.Environment, attr) is None and getattr(catch.Catch, attr) is None
-    # the refusals are the evaluation's, through its check functions
-    src = inspect.getsource(fn)
-    assert f'self._check_evaluate_{kind}(' in src and '_ensure_allocated()' in src
-    assert src.index(f'_check_evaluate_{kind}(') < src.index('_check_trajectory_slab(') < src.index('_ensure_allocated()')
+    abi = lambda cls: cls._closed_loop_abi(object.__new__(cls), f'rollout_{kind}')      # pylint: disable=protected-access,cell-var-from-loop
+    assert abi(cartpole.Cartpole) == abi(cartpole.CartpoleSwingup) == ENTRY['cartpole', kind]
+    assert abi(mountain_car.MountainCar) == ENTRY['mountain_car', kind] and ENTRY['cartpole', kind] in _native.EXPORTED
+    assert abi(base.Environment) is None and abi(catch.Catch) is None and ENTRY['mountain_car', kind] in _native.EXPORTED
+    # the refusals are the evaluation's, in its words, then the slab: two faults at a time, the earlier one's message, and
+    # nothing allocated after the last
+    for env in _envs():
+      D, first = _dim(env), 'weights' if kind == 'linear' else 'w1'
+      shapes = dict(weights=(3, D + 1)) if kind == 'linear' else dict(w1=(5, D + 1), w2=(3, 6))
+      env._device = torch.device('cpu')
+      bad = dict({k: torch.zeros(v) for k, v in shapes.items()}, observation=torch.zeros((4, D)), **{first: None})
+      said = []
+      for call in (f'rollout_{kind}', f'evaluate_{kind}'):
+        said.append(str(pytest.raises(ValueError, getattr(env, call), *bad.values(), 4).value).replace(call, ''))
+      assert said[0] == said[1] and f'{first} must be' in said[0]
+      env._device = torch.device('meta')                                   # tensors without storage: a slab of 4 GiB passes the
+      env._batch = -(-(1 << 32) // (4 * D))                                # arguments' checks
+      big = dict({k: torch.zeros(v, device='meta') for k, v in shapes.items()}, observation=torch.zeros((env._batch, D), device='meta'))
+      idx = torch.zeros(env._batch, dtype=torch.int32, device='meta')
+      _refused(env, kind, match='must be None', policy_index=idx, **big)
+      _refused(env, kind, match='4 GiB', **big)
 
 
 def test_views_families_and_modes_are_refused():
