@@ -151,56 +151,44 @@ __device__ __forceinline__ void bsx_drawn_returns_body(bsx_drawn_returns_kernarg
 int bsx_launch_drawn_returns(const bsx_drawn_returns_args& a, hipStream_t st);
 
 // The refusals of the four entry points that do not depend on the family: bsx_check_linear_call's / bsx_check_mlp_call's, in
-// their order, with the rule of bsx_check_gumbel_call where the evaluation refuses an epsilon outside [0, 1] — an epsilon
-// other than 0.0 (NaN included) or an inv_temperature that is not finite or not > 0 is BSX_ERANGE.  The check is given a copy
-// of the policy whose epsilon is 0.0 when both are acceptable and out of range when either is not.  No slab is written, so
-// there is no 4 GiB refusal.
-template <class Policy>
-static inline Policy bsx_drawn_returns_checked(const Policy* policy, double inv_temperature) {
-  Policy q = *policy;
-  const bool ok = policy->epsilon == 0.0 && __builtin_isfinite(inv_temperature) && inv_temperature > 0.0;
-  q.epsilon = ok ? 0.0 : 2.0;
-  return q;
-}
+// their order, for the policy under the drawn rule (bsx_drawn_policy, bsx_linear_score.h).  No slab is written, so there is
+// no 4 GiB refusal.
 static inline int bsx_check_drawn_returns_call(const bsx_call_t* call, const bsx_linear_t* lin, double inv_temperature,
                                                const float* state, const int32_t* steps, const bsx_linear_eval_t& out,
                                                const double* info, const void* extra) {
-  const bsx_linear_t q = bsx_drawn_returns_checked(lin, inv_temperature);
+  const bsx_linear_t q = bsx_drawn_policy(lin, inv_temperature);
   return bsx_check_linear_call(call, &q, state, steps, out, info, extra);
 }
 static inline int bsx_check_drawn_returns_call(const bsx_call_t* call, const bsx_mlp_t* mlp, double inv_temperature,
                                                const float* state, const int32_t* steps, const bsx_linear_eval_t& out,
                                                const double* info, const void* extra) {
-  const bsx_mlp_t q = bsx_drawn_returns_checked(mlp, inv_temperature);
+  const bsx_mlp_t q = bsx_drawn_policy(mlp, inv_temperature);
   return bsx_check_mlp_call(call, &q, state, steps, out, info, extra);
 }
 
-// What the entry points share once the family's args are in place (a.fam).
-static inline int bsx_drawn_returns_fill(bsx_drawn_returns_args& a, int32_t family, const bsx_call_t* call, const float* w1,
-                                         const float* w2, int32_t n_policies, int32_t hidden, const int32_t* policy_index,
-                                         const float* observation_in, uint64_t sample_seed, double inv_temperature,
-                                         const bsx_linear_eval_t& out) {
+// What the entry points share once the family's args are in place (a.fam): policy->explore_seed is the sample seed.
+template <class Policy>
+static inline int bsx_drawn_returns_call(bsx_drawn_returns_args& a, int32_t family, const bsx_call_t* call, const Policy* policy,
+                                         double inv_temperature, const bsx_linear_eval_t& out) {
   a.family = family;
   a.n_steps = call->n_steps;
-  a.p.w1 = w1; a.p.w2 = w2;
-  a.p.policy_index = n_policies > 1 ? policy_index : nullptr;
-  a.p.observation_in = observation_in;
+  a.p = bsx_make_trajectory_policy(policy);
   a.p.epsilon = 0.0;
-  a.p.explore_seed = sample_seed;
-  a.p.n_policies = n_policies; a.p.hidden = hidden;
   a.beta = inv_temperature;
   a.out = out;
   return bsx_launch_drawn_returns(a, (hipStream_t)call->hip_stream);
 }
-static inline int bsx_drawn_returns_call(bsx_drawn_returns_args& a, int32_t family, const bsx_call_t* call, const bsx_linear_t* lin,
-                                         double inv_temperature, const bsx_linear_eval_t& out) {
-  return bsx_drawn_returns_fill(a, family, call, lin->weights, nullptr, lin->n_policies, 0, lin->policy_index, lin->observation_in,
-                                lin->explore_seed, inv_temperature, out);
-}
-static inline int bsx_drawn_returns_call(bsx_drawn_returns_args& a, int32_t family, const bsx_call_t* call, const bsx_mlp_t* mlp,
-                                         double inv_temperature, const bsx_linear_eval_t& out) {
-  return bsx_drawn_returns_fill(a, family, call, mlp->w1, mlp->w2, mlp->n_policies, mlp->hidden, mlp->policy_index,
-                                mlp->observation_in, mlp->explore_seed, inv_temperature, out);
+
+// bsx_<family>_linear_sample_evaluate / bsx_<family>_mlp_sample_evaluate (Fam: the family's host trait, bsx_host.h).
+template <class Fam, class Policy>
+static inline int bsx_drawn_returns_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const Policy* policy,
+                                          double inv_temperature, float* state, int32_t* steps, const bsx_linear_eval_t& out,
+                                          double* info) {
+  bsx_drawn_returns_args e;
+  return bsx_physics_closed_loop<Fam>(
+      cfg, call, policy, state, steps, info, e.fam,
+      [&](const void* extra, int) { return bsx_check_drawn_returns_call(call, policy, inv_temperature, state, steps, out, info, extra); },
+      [&](int32_t family) { return bsx_drawn_returns_call(e, family, call, policy, inv_temperature, out); });
 }
 
 #endif  // BSX_DRAWN_RETURNS_H_

@@ -410,4 +410,45 @@ static inline int bsx_embed_sample_call(bsx_embed_args& a, int32_t family, const
   return bsx_embed_fill_and_launch(a, family, call, &em, record, true, sm->inv_temperature, rows, out);
 }
 
+// bsx_<family>_embedding_rollout / _embedding_evaluate and _embedding_sample / _embedding_sample_evaluate: a recording call by
+// its TimeStep, an evaluation by its three columns (Fam: the family's host trait, bsx_host.h).
+template <class Fam>
+static inline int bsx_embed_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                  int32_t* state, const bsx_timestep_t& out, double* info) {
+  bsx_embed_args s;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, &out, info, Fam::of(s.fam),
+      [&] { return bsx_check_embed_call(call, policy, Fam::cells(cfg), Fam::actions, state, out, info); },
+      [&] { return bsx_embed_call(s, Fam::code, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{}); });
+}
+template <class Fam>
+static inline int bsx_embed_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
+                                  int32_t* state, const bsx_policy_eval_t& out, double* info) {
+  bsx_embed_args s;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, nullptr, info, Fam::of(s.fam),
+      [&] { return bsx_check_embed_eval_call(call, policy, Fam::cells(cfg), Fam::actions, state, out, info); },
+      [&] { return bsx_embed_call(s, Fam::code, call, policy, false, nullptr, out); });
+}
+template <class Fam>
+static inline int bsx_embed_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                  int32_t* state, const bsx_timestep_t& out, double* info) {
+  bsx_embed_args s;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, &out, info, Fam::of(s.fam),
+      [&] { return bsx_check_embed_sample_call(call, policy, Fam::cells(cfg), Fam::actions, state, out, info); },
+      [&] {
+        return bsx_embed_sample_call(s, Fam::code, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+      });
+}
+template <class Fam>
+static inline int bsx_embed_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                  int32_t* state, const bsx_policy_eval_t& out, double* info) {
+  bsx_embed_args s;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, nullptr, info, Fam::of(s.fam),
+      [&] { return bsx_check_embed_sample_eval_call(call, policy, Fam::cells(cfg), Fam::actions, state, out, info); },
+      [&] { return bsx_embed_sample_call(s, Fam::code, call, policy, false, nullptr, out); });
+}
+
 #endif  // BSX_EMBED_DEVICE_H_

@@ -162,47 +162,40 @@ __device__ __forceinline__ void bsx_gumbel_body(bsx_gumbel_kernarg ka, float* s_
 // Launches bsx_gumbel_kernel over a.t.fam's lanes (the caller has checked that the grid fits).
 int bsx_launch_gumbel(const bsx_gumbel_args& a, hipStream_t st);
 
-// The refusals of the four entry points that do not depend on the family: bsx_check_trajectory_call's, in its order.  What
-// is new has one place in that order — where the evaluation refuses an epsilon outside [0, 1] (BSX_ERANGE: after the modes
-// and the scalars, before an empty call returns and before any pointer is looked at): a sampled call refuses there an epsilon
-// other than 0.0 (NaN included) and an inv_temperature that is not finite or not > 0.  The check is given a copy of the policy
-// whose epsilon is 0.0 when both are acceptable and out of range when either is not.
+// The refusals of the four entry points that do not depend on the family: bsx_check_trajectory_call's, in its order, for
+// the policy under the drawn rule (bsx_drawn_policy, bsx_linear_score.h).
 template <class Policy>
 static inline int bsx_check_gumbel_call(const bsx_call_t* call, const Policy* policy, double inv_temperature, const float* state,
                                         const int32_t* steps, const bsx_timestep_t& out, const int32_t* actions_out,
                                         const double* info, const void* extra, int D) {
-  Policy q = *policy;
-  const bool ok = policy->epsilon == 0.0 && __builtin_isfinite(inv_temperature) && inv_temperature > 0.0;
-  q.epsilon = ok ? 0.0 : 2.0;
+  const Policy q = bsx_drawn_policy(policy, inv_temperature);
   return bsx_check_trajectory_call(call, &q, state, steps, out, actions_out, info, extra, D);
 }
 
-// What the entry points share once the family's args are in place (a.t.fam).
-static inline void bsx_gumbel_fill(bsx_gumbel_args& a, int32_t family, const bsx_call_t* call, const float* w1, const float* w2,
-                                   int32_t n_policies, int32_t hidden, const int32_t* policy_index, const float* observation_in,
-                                   uint64_t sample_seed, double inv_temperature, const bsx_timestep_t& out, int32_t* actions_out) {
+// What the entry points share once the family's args are in place (a.t.fam): policy->explore_seed is the sample seed.
+template <class Policy>
+static inline int bsx_gumbel_call(bsx_gumbel_args& a, int32_t family, const bsx_call_t* call, const Policy* policy,
+                                  double inv_temperature, const bsx_timestep_t& out, int32_t* actions_out) {
   a.t.family = family;
   a.t.n_steps = call->n_steps;
-  a.t.p.w1 = w1; a.t.p.w2 = w2;
-  a.t.p.policy_index = n_policies > 1 ? policy_index : nullptr;
-  a.t.p.observation_in = observation_in;
+  a.t.p = bsx_make_trajectory_policy(policy);
   a.t.p.epsilon = 0.0;
-  a.t.p.explore_seed = sample_seed;
-  a.t.p.n_policies = n_policies; a.t.p.hidden = hidden;
   a.t.out = out; a.t.actions_out = actions_out;
   a.beta = inv_temperature;
-}
-static inline int bsx_gumbel_call(bsx_gumbel_args& a, int32_t family, const bsx_call_t* call, const bsx_linear_t* lin,
-                                  double inv_temperature, const bsx_timestep_t& out, int32_t* actions_out) {
-  bsx_gumbel_fill(a, family, call, lin->weights, nullptr, lin->n_policies, 0, lin->policy_index, lin->observation_in,
-                  lin->explore_seed, inv_temperature, out, actions_out);
   return bsx_launch_gumbel(a, (hipStream_t)call->hip_stream);
 }
-static inline int bsx_gumbel_call(bsx_gumbel_args& a, int32_t family, const bsx_call_t* call, const bsx_mlp_t* mlp,
-                                  double inv_temperature, const bsx_timestep_t& out, int32_t* actions_out) {
-  bsx_gumbel_fill(a, family, call, mlp->w1, mlp->w2, mlp->n_policies, mlp->hidden, mlp->policy_index, mlp->observation_in,
-                  mlp->explore_seed, inv_temperature, out, actions_out);
-  return bsx_launch_gumbel(a, (hipStream_t)call->hip_stream);
+
+// bsx_<family>_linear_sample / bsx_<family>_mlp_sample (Fam: the family's host trait, bsx_host.h).
+template <class Fam, class Policy>
+static inline int bsx_gumbel_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const Policy* policy, double inv_temperature,
+                                   float* state, int32_t* steps, const bsx_timestep_t& out, int32_t* actions_out, double* info) {
+  bsx_gumbel_args e;
+  return bsx_physics_closed_loop<Fam>(
+      cfg, call, policy, state, steps, info, e.t.fam,
+      [&](const void* extra, int D) {
+        return bsx_check_gumbel_call(call, policy, inv_temperature, state, steps, out, actions_out, info, extra, D);
+      },
+      [&](int32_t family) { return bsx_gumbel_call(e, family, call, policy, inv_temperature, out, actions_out); });
 }
 
 #endif  // BSX_GUMBEL_DEVICE_H_

@@ -1,4 +1,5 @@
-// bsx_host.h — host-side glue shared by the C-ABI entry points (argument checks, launch math).
+// bsx_host.h — host-side glue shared by the C-ABI entry points (argument checks, launch math, the grouped launch, the one
+// prologue of the fused closed-loop calls).
 #ifndef BSX_HOST_H_
 #define BSX_HOST_H_
 
@@ -187,5 +188,58 @@ static inline int bsx_group_check_set(bsx_group* g, int32_t family, int32_t inde
 }
 
 static inline int bsx_launch_status() { return (int)hipGetLastError(); }
+
+// ---------------------------------------------------------------------------------------------
+// The host-side prologue of the forty fused closed-loop entry points bsx_<family>_<kind>_<verb>, once per group of
+// families.  A family's .hip defines a host trait `Fam` with what differs between the families; a kind's header gives its
+// family-free refusals (`check`) and its fill-and-launch (`launch`) and states each entry's body once, as a template over
+// Fam; the extern "C" definitions in the family's .hip are one-statement delegations.  The order of the refusals is the
+// documented one (include/bsuite_amd.h): null structs, the cfg's range, the kind's modes / scalars / pointers, an empty
+// call (code 0), and only then the kernel's arguments and whatever the launch itself refuses (the grid bound).
+//
+// cartpole, mountain_car (linear, mlp, mlp2).  Fam:
+//   cfg_t, env, code    the cfg struct, the device-side family (env::args), BSX_FAM_*
+//   range(cfg, a)       the cfg's range check — 0 or BSX_ERANGE — leaving what it derives from the cfg in *a
+//   obs_numel(cfg)      floats per observation row;  extra(cfg): a pointer only the family needs, or any non-null
+//   fill(cfg, call, action, state, steps, out, info, a)   the rest of *a (the family's make() fills through it too)
+//   of(fam)             the family's member of a kernel's `fam` union
+// `fam` is that union in the kind's argument struct; check(extra, D) and launch(family code) are the kind's.
+template <class Fam, class Union, class Policy, class Check, class Launch>
+static inline int bsx_physics_closed_loop(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const Policy* policy, float* state,
+                                          int32_t* steps, double* info, Union& fam, Check check, Launch launch) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  typename Fam::env::args* a = Fam::of(fam);
+  int rc = Fam::range(cfg, a);
+  if (rc == 0) rc = check(Fam::extra(cfg), Fam::obs_numel(cfg));
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  // (no action column; no TimeStep: a recording kernel reads its own struct's)
+  Fam::fill(cfg, call, nullptr, state, steps, bsx_timestep_t{}, info, a);
+  return launch(Fam::code);
+}
+
+// deep_sea, catch (policy, embedding).  Fam:
+//   cfg_t, fam, hot_t, code, actions    the cfg struct, the device-side family (fam::args), its hot-cell functor, BSX_FAM_*, |A|
+//   check_cfg(cfg), states(cfg), cells(cfg), hot(cfg)    the cfg's range check, the table length, the board's cells, the functor
+//   make(...) / fill(...)               the family's checked / unchecked kernel arguments (step and the groups use make too)
+//   of(fam)                             the family's member of a kernel's `fam` union
+// `record`: the [T,B] TimeStep of a recording call — its *a comes from make() with actions_out standing in for the action
+// column in the common checks, and no action column is read — or null: an evaluation has no action column and no TimeStep.
+template <class Fam, class Policy, class Check, class Launch>
+static inline int bsx_grid_closed_loop(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const Policy* policy, int32_t* state,
+                                       const bsx_timestep_t* record, double* info, typename Fam::fam::args* a, Check check,
+                                       Launch launch) {
+  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
+  int rc = Fam::check_cfg(cfg);
+  if (rc == 0) rc = check();
+  if (rc != 0 || call->n_lanes == 0) return rc;
+  if (record != nullptr) {
+    rc = Fam::make(cfg, call, policy->actions_out, state, *record, info, a);
+    if (rc != 0) return rc;
+    a->action = nullptr;
+  } else {
+    Fam::fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, a);
+  }
+  return launch();
+}
 
 #endif  // BSX_HOST_H_

@@ -198,4 +198,27 @@ static inline int bsx_linear_score_call(bsx_linear_score_args& a, int32_t family
   return bsx_launch_linear_score(a, (hipStream_t)call->hip_stream);
 }
 
+// bsx_<family>_linear_evaluate (Fam: the family's host trait, bsx_host.h).
+template <class Fam>
+static inline int bsx_linear_score_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_linear_t* lin, float* state,
+                                         int32_t* steps, const bsx_linear_eval_t& out, double* info) {
+  bsx_linear_score_args e;
+  return bsx_physics_closed_loop<Fam>(
+      cfg, call, lin, state, steps, info, e.fam,
+      [&](const void* extra, int) { return bsx_check_linear_call(call, lin, state, steps, out, info, extra); },
+      [&](int32_t family) { return bsx_linear_score_call(e, family, call, lin, out); });
+}
+
+// The rule of every drawn (softmax) physics call, stated where the greedy calls refuse an epsilon outside [0, 1] (BSX_ERANGE:
+// after the modes and the scalars, before an empty call returns and before any pointer is looked at): an epsilon other than
+// 0.0 (NaN included) or an inv_temperature that is not finite or not > 0 is refused there.  The greedy check is given this
+// copy of the policy, whose epsilon is 0.0 when both are acceptable and out of range when either is not.
+template <class Policy>
+static inline Policy bsx_drawn_policy(const Policy* policy, double inv_temperature) {
+  Policy q = *policy;
+  const bool ok = policy->epsilon == 0.0 && __builtin_isfinite(inv_temperature) && inv_temperature > 0.0;
+  q.epsilon = ok ? 0.0 : 2.0;
+  return q;
+}
+
 #endif  // BSX_LINEAR_SCORE_H_

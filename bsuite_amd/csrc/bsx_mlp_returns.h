@@ -199,4 +199,15 @@ static inline int bsx_mlp_returns_call(bsx_mlp_returns_args& a, int32_t family, 
   return bsx_launch_mlp_returns(a, (hipStream_t)call->hip_stream);
 }
 
+// bsx_<family>_mlp_evaluate (Fam: the family's host trait, bsx_host.h).
+template <class Fam>
+static inline int bsx_mlp_returns_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, float* state,
+                                        int32_t* steps, const bsx_linear_eval_t& out, double* info) {
+  bsx_mlp_returns_args e;
+  return bsx_physics_closed_loop<Fam>(
+      cfg, call, mlp, state, steps, info, e.fam,
+      [&](const void* extra, int) { return bsx_check_mlp_call(call, mlp, state, steps, out, info, extra); },
+      [&](int32_t family) { return bsx_mlp_returns_call(e, family, call, mlp, out); });
+}
+
 #endif  // BSX_MLP_RETURNS_H_

@@ -211,6 +211,17 @@ static int bsx_policy_rollout_call(const typename Fam::args& a, const bsx_call_t
   return bsx_launch_status();
 }
 
+// bsx_<family>_policy_rollout (Fam: the family's host trait, bsx_host.h).
+template <class Fam>
+static int bsx_policy_rollout_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy, int32_t* state,
+                                    const bsx_timestep_t& out, double* info) {
+  typename Fam::fam::args a;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, &out, info, &a,
+      [&] { return bsx_check_policy_call(call, policy, Fam::states(cfg), state, out, info); },
+      [&] { return bsx_policy_rollout_call<typename Fam::fam, typename Fam::hot_t>(a, call, policy, Fam::actions, out, Fam::hot(cfg)); });
+}
+
 // One call of a two-kernel family (deep_sea, catch): step() / reset() / a rollout of T steps with outputs
 // [T,B,...].  `a` comes from the family's make(); K = stores per thread of its observation stream.
 //   delta mode (obs_paint)          one launch per step: advance + in-place patch

@@ -33,4 +33,15 @@ static inline int bsx_tab_eval_call(bsx_tab_eval_args& a, int32_t family, const 
   return bsx_launch_tab_eval(a, (hipStream_t)call->hip_stream);
 }
 
+// bsx_<family>_policy_evaluate (Fam: the family's host trait, bsx_host.h).
+template <class Fam>
+static inline int bsx_tab_eval_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy, int32_t* state,
+                                     const bsx_policy_eval_t& out, double* info) {
+  bsx_tab_eval_args e;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, nullptr, info, Fam::of(e.fam),
+      [&] { return bsx_check_policy_eval_call(call, policy, Fam::states(cfg), state, out, info); },
+      [&] { return bsx_tab_eval_call(e, Fam::code, call, policy, Fam::actions, out); });
+}
+
 #endif  // BSX_TAB_EVAL_H_

@@ -277,4 +277,26 @@ static inline int bsx_tab_softmax_call(bsx_tab_softmax_args& a, int32_t family, 
   return bsx_launch_tab_softmax(a, (hipStream_t)call->hip_stream);
 }
 
+// bsx_<family>_policy_sample / bsx_<family>_policy_sample_evaluate (Fam: the family's host trait, bsx_host.h).
+template <class Fam>
+static inline int bsx_tab_softmax_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                                        int32_t* state, const bsx_timestep_t& out, double* info) {
+  bsx_tab_softmax_args s;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, &out, info, Fam::of(s.fam),
+      [&] { return bsx_check_tab_softmax_call(call, policy, Fam::states(cfg), Fam::actions, state, out, info); },
+      [&] {
+        return bsx_tab_softmax_call(s, Fam::code, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+      });
+}
+template <class Fam>
+static inline int bsx_tab_softmax_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                                        int32_t* state, const bsx_policy_eval_t& out, double* info) {
+  bsx_tab_softmax_args s;
+  return bsx_grid_closed_loop<Fam>(
+      cfg, call, policy, state, nullptr, info, Fam::of(s.fam),
+      [&] { return bsx_check_tab_softmax_eval_call(call, policy, Fam::states(cfg), Fam::actions, state, out, info); },
+      [&] { return bsx_tab_softmax_call(s, Fam::code, call, policy, false, nullptr, out); });
+}
+
 #endif  // BSX_TAB_SAMPLE_DEVICE_H_

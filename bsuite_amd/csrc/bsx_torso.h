@@ -363,16 +363,11 @@ static inline int bsx_check_mlp2_call(const bsx_call_t* call, const bsx_mlp2_t* 
   return bsx_check_mlp_call(call, &one, state, steps, outputs_present, info, m->w3 != nullptr ? extra : nullptr);
 }
 
-// ... and of the four sampled entry points (bsx_<family>_mlp2_sample, bsx_<family>_mlp2_sample_evaluate): the same, with the
-// rule of bsx_check_gumbel_call where the greedy calls refuse an epsilon outside [0, 1] (BSX_ERANGE: after the modes and the
-// scalars, before an empty call returns and before any pointer is looked at) — an epsilon other than 0.0 (NaN included) or an
-// inv_temperature that is not finite or not > 0.  The check is given a copy of the policy whose epsilon is 0.0 when both are
-// acceptable and out of range when either is not.
+// ... and of the four sampled entry points (bsx_<family>_mlp2_sample, bsx_<family>_mlp2_sample_evaluate): the same, for the
+// policy under the drawn rule (bsx_drawn_policy, bsx_linear_score.h).
 static inline int bsx_check_mlp2_sample_call(const bsx_call_t* call, const bsx_mlp2_t* m, double inv_temperature, const float* state,
                                              const int32_t* steps, bool outputs_present, const double* info, const void* extra) {
-  bsx_mlp2_t q = *m;
-  const bool ok = m->epsilon == 0.0 && __builtin_isfinite(inv_temperature) && inv_temperature > 0.0;
-  q.epsilon = ok ? 0.0 : 2.0;
+  const bsx_mlp2_t q = bsx_drawn_policy(m, inv_temperature);
   return bsx_check_mlp2_call(call, &q, state, steps, outputs_present, info, extra);
 }
 
@@ -396,6 +391,25 @@ static inline int bsx_torso_call(bsx_torso_args& a, int32_t family, const bsx_ca
   a.ev = ev; a.out = out; a.actions_out = actions_out;
   a.beta = mode == BSX_TORSO_DRAWN ? inv_temperature : 1.0;
   return bsx_launch_torso(a, (hipStream_t)call->hip_stream);
+}
+
+// bsx_<family>_mlp2_evaluate / _mlp2_rollout (BSX_TORSO_GREEDY) and _mlp2_sample_evaluate / _mlp2_sample (BSX_TORSO_DRAWN), returns
+// only or recorded (Fam: the family's host trait, bsx_host.h).  A recording call refuses last what bsx_check_trajectory_call
+// refuses last: the 4 GiB slab.
+template <class Fam>
+static inline int bsx_torso_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, int32_t mode,
+                                  double inv_temperature, float* state, int32_t* steps, bool record, const bsx_linear_eval_t& ev,
+                                  const bsx_timestep_t& out, int32_t* actions_out, double* info) {
+  bsx_torso_args e;
+  return bsx_physics_closed_loop<Fam>(
+      cfg, call, mlp2, state, steps, info, e.fam,
+      [&](const void* extra, int D) {
+        const bool present = record ? bsx_trajectory_outputs_present(out, actions_out) : bsx_linear_eval_present(ev);
+        const int rc = mode == BSX_TORSO_DRAWN ? bsx_check_mlp2_sample_call(call, mlp2, inv_temperature, state, steps, present, info, extra)
+                                               : bsx_check_mlp2_call(call, mlp2, state, steps, present, info, extra);
+        return record ? bsx_check_trajectory_slab(rc, call, D) : rc;
+      },
+      [&](int32_t family) { return bsx_torso_call(e, family, call, mlp2, mode, inv_temperature, record, ev, out, actions_out); });
 }
 
 #endif  // BSX_TORSO_H_

@@ -245,32 +245,37 @@ static inline int bsx_check_trajectory_call(const bsx_call_t* call, const bsx_ml
       bsx_check_mlp_call(call, mlp, state, steps, bsx_trajectory_outputs_present(out, actions_out), info, extra), call, D);
 }
 
+// The policy side of a call as the kernel reads it, from either kind of policy struct (epsilon and explore_seed as given:
+// a drawn call overwrites the one and reads the other as its sample seed).
+static inline bsx_trajectory_policy bsx_make_trajectory_policy(const bsx_linear_t* lin) {
+  return {lin->weights, nullptr, lin->n_policies > 1 ? lin->policy_index : nullptr, lin->observation_in, lin->epsilon,
+          lin->explore_seed, lin->n_policies, 0};
+}
+static inline bsx_trajectory_policy bsx_make_trajectory_policy(const bsx_mlp_t* mlp) {
+  return {mlp->w1, mlp->w2, mlp->n_policies > 1 ? mlp->policy_index : nullptr, mlp->observation_in, mlp->epsilon,
+          mlp->explore_seed, mlp->n_policies, mlp->hidden};
+}
+
 // What the entry points share once the family's args are in place.
-static inline int bsx_trajectory_call(bsx_trajectory_args& a, int32_t family, const bsx_call_t* call, const bsx_linear_t* lin,
+template <class Policy>
+static inline int bsx_trajectory_call(bsx_trajectory_args& a, int32_t family, const bsx_call_t* call, const Policy* policy,
                                       const bsx_timestep_t& out, int32_t* actions_out) {
   a.family = family;
   a.n_steps = call->n_steps;
-  a.p.w1 = lin->weights; a.p.w2 = nullptr;
-  a.p.policy_index = lin->n_policies > 1 ? lin->policy_index : nullptr;
-  a.p.observation_in = lin->observation_in;
-  a.p.epsilon = lin->epsilon;
-  a.p.explore_seed = lin->explore_seed;
-  a.p.n_policies = lin->n_policies; a.p.hidden = 0;
+  a.p = bsx_make_trajectory_policy(policy);
   a.out = out; a.actions_out = actions_out;
   return bsx_launch_trajectory(a, (hipStream_t)call->hip_stream);
 }
-static inline int bsx_trajectory_call(bsx_trajectory_args& a, int32_t family, const bsx_call_t* call, const bsx_mlp_t* mlp,
-                                      const bsx_timestep_t& out, int32_t* actions_out) {
-  a.family = family;
-  a.n_steps = call->n_steps;
-  a.p.w1 = mlp->w1; a.p.w2 = mlp->w2;
-  a.p.policy_index = mlp->n_policies > 1 ? mlp->policy_index : nullptr;
-  a.p.observation_in = mlp->observation_in;
-  a.p.epsilon = mlp->epsilon;
-  a.p.explore_seed = mlp->explore_seed;
-  a.p.n_policies = mlp->n_policies; a.p.hidden = mlp->hidden;
-  a.out = out; a.actions_out = actions_out;
-  return bsx_launch_trajectory(a, (hipStream_t)call->hip_stream);
+
+// bsx_<family>_linear_rollout / bsx_<family>_mlp_rollout (Fam: the family's host trait, bsx_host.h).
+template <class Fam, class Policy>
+static inline int bsx_trajectory_entry(const typename Fam::cfg_t* cfg, const bsx_call_t* call, const Policy* policy, float* state,
+                                       int32_t* steps, const bsx_timestep_t& out, int32_t* actions_out, double* info) {
+  bsx_trajectory_args e;
+  return bsx_physics_closed_loop<Fam>(
+      cfg, call, policy, state, steps, info, e.fam,
+      [&](const void* extra, int D) { return bsx_check_trajectory_call(call, policy, state, steps, out, actions_out, info, extra, D); },
+      [&](int32_t family) { return bsx_trajectory_call(e, family, call, policy, out, actions_out); });
 }
 
 #endif  // BSX_TRAJECTORY_H_

@@ -2,6 +2,8 @@
 // Device code: cartpole_env.h on the skeleton of small_obs.h.  One translation unit per small-observation family: the families' kernels are independent
 // template instantiations, and compiling them side by side is what keeps a clean build() under a minute (round 6; as ONE
 // file they were a 56 s single-threaded compile, the long pole of every build).
+// Host code: the family's host trait (cartpole_host), make() for step and the groups, and the extern "C" definitions — the twelve
+// fused closed-loop ones are one-statement delegations ("Host glue of the closed-loop calls").
 #include "small_obs.h"
 #include "bsx_linear_score.h"
 #include "bsx_mlp_returns.h"
@@ -28,6 +30,27 @@ static int cartpole_derive(const bsx_cartpole_t* cfg, cartpole_env::args* a) {
   return 0;
 }
 
+// What differs between the physics families on the host: the trait of bsx_physics_closed_loop (bsx_host.h).
+namespace {                                 // (internal linkage: the library exports its C ABI and nothing else)
+struct cartpole_host {
+  typedef bsx_cartpole_t cfg_t;
+  typedef cartpole_env env;
+  static constexpr int32_t code = BSX_FAM_CARTPOLE;
+  static int range(const cfg_t* cfg, env::args* a) {
+    return (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
+  }
+  static int obs_numel(const cfg_t* cfg) { return cfg->swingup ? 8 : 6; }
+  static const void* extra(const cfg_t* cfg) { return cfg->time_frac; }
+  static void fill(const cfg_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps,
+                   const bsx_timestep_t& out, double* info, env::args* a) {
+    a->ctl = bsx_make_ctl(call); a->action = action; a->state = state; a->steps = steps; a->out = out;
+    a->info = info; a->obs_numel = obs_numel(cfg); a->cfg = *cfg;
+  }
+  template <class Union>
+  static env::args* of(Union& fam) { return &fam.cartpole; }
+};
+}  // namespace
+
 static int cartpole_make(const bsx_cartpole_t* cfg, const bsx_call_t* call, const int32_t* action, float* state, int32_t* steps, bsx_timestep_t out, double* info, cartpole_env::args* a) {
   if (cfg == nullptr) return BSX_ENULL;
   int rc = bsx_check_call(call, action, out);
@@ -35,8 +58,7 @@ static int cartpole_make(const bsx_cartpole_t* cfg, const bsx_call_t* call, cons
   if (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) return BSX_ERANGE;
   if (call->n_lanes > 0 && (state == nullptr || steps == nullptr || info == nullptr || cfg->time_frac == nullptr))
     return BSX_ENULL;
-  a->ctl = bsx_make_ctl(call); a->action = action; a->state = state; a->steps = steps; a->out = out;
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
+  cartpole_host::fill(cfg, call, action, state, steps, out, info, a);
   return cartpole_derive(cfg, a);
 }
 
@@ -48,150 +70,74 @@ extern "C" int bsx_cartpole_step(const bsx_cartpole_t* cfg, const bsx_call_t* ca
   return launch_small_obs<cartpole_env>(a, bsx_n_steps(call), call->hip_stream);
 }
 
-extern "C" int bsx_cartpole_linear_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear, float* state,
-                                             int32_t* steps, bsx_linear_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || linear == nullptr) return BSX_ENULL;
-  bsx_linear_score_args e;
-  cartpole_env::args* a = &e.fam.cartpole;
-  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
-  if (rc == 0) rc = bsx_check_linear_call(call, linear, state, steps, out, info, cfg->time_frac);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_linear_score_call(e, BSX_FAM_CARTPOLE, call, linear, out);
+// The twelve fused closed-loop entry points: each body is stated once for both families, beside its kind's checks
+// (bsx_<kind>_entry in bsx_linear_score.h ... bsx_drawn_returns.h), over the one prologue of bsx_host.h.
+extern "C" int bsx_cartpole_linear_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                            float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return bsx_linear_score_entry<cartpole_host>(cfg, call, linear, state, steps, out, info);
 }
 
-extern "C" int bsx_cartpole_mlp_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, float* state,
-                                          int32_t* steps, bsx_linear_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || mlp == nullptr) return BSX_ENULL;
-  bsx_mlp_returns_args e;
-  cartpole_env::args* a = &e.fam.cartpole;
-  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
-  if (rc == 0) rc = bsx_check_mlp_call(call, mlp, state, steps, out, info, cfg->time_frac);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_mlp_returns_call(e, BSX_FAM_CARTPOLE, call, mlp, out);
+extern "C" int bsx_cartpole_mlp_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                         float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return bsx_mlp_returns_entry<cartpole_host>(cfg, call, mlp, state, steps, out, info);
 }
 
 // rollout_linear / rollout_mlp: the two evaluations' closed loop, writing the [T,B] TimeSteps and the actions taken.
-template <class Policy>
-static int cartpole_trajectory(const bsx_cartpole_t* cfg, const bsx_call_t* call, const Policy* policy, float* state, int32_t* steps,
-                               const bsx_timestep_t& out, int32_t* actions_out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  bsx_trajectory_args e;
-  cartpole_env::args* a = &e.fam.cartpole;
-  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
-  if (rc == 0) rc = bsx_check_trajectory_call(call, policy, state, steps, out, actions_out, info, cfg->time_frac, cfg->swingup ? 8 : 6);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.out)
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_trajectory_call(e, BSX_FAM_CARTPOLE, call, policy, out, actions_out);
+extern "C" int bsx_cartpole_linear_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
+                                           float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return bsx_trajectory_entry<cartpole_host>(cfg, call, linear, state, steps, out, actions_out, info);
 }
 
-extern "C" int bsx_cartpole_linear_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear, float* state,
-                                            int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return cartpole_trajectory(cfg, call, linear, state, steps, out, actions_out, info);
-}
-
-extern "C" int bsx_cartpole_mlp_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, float* state,
-                                         int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return cartpole_trajectory(cfg, call, mlp, state, steps, out, actions_out, info);
+extern "C" int bsx_cartpole_mlp_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
+                                        float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return bsx_trajectory_entry<cartpole_host>(cfg, call, mlp, state, steps, out, actions_out, info);
 }
 
 // evaluate_mlp2 / rollout_mlp2 (BSX_TORSO_GREEDY) and evaluate_sampled_mlp2 / sample_mlp2 (BSX_TORSO_DRAWN): the closed loop
 // under a policy with two ReLU hidden layers, returns only or recorded.
-static int cartpole_torso(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, int32_t mode,
-                          double inv_temperature, float* state, int32_t* steps, bool record, const bsx_linear_eval_t& ev,
-                          const bsx_timestep_t& out, int32_t* actions_out, double* info) {
-  if (cfg == nullptr || call == nullptr || mlp2 == nullptr) return BSX_ENULL;
-  bsx_torso_args e;
-  cartpole_env::args* a = &e.fam.cartpole;
-  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
-  const bool present = record ? bsx_trajectory_outputs_present(out, actions_out) : bsx_linear_eval_present(ev);
-  if (rc == 0)
-    rc = mode == BSX_TORSO_DRAWN ? bsx_check_mlp2_sample_call(call, mlp2, inv_temperature, state, steps, present, info, cfg->time_frac)
-                                 : bsx_check_mlp2_call(call, mlp2, state, steps, present, info, cfg->time_frac);
-  if (record) rc = bsx_check_trajectory_slab(rc, call, cfg->swingup ? 8 : 6);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.out)
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_torso_call(e, BSX_FAM_CARTPOLE, call, mlp2, mode, inv_temperature, record, ev, out, actions_out);
+extern "C" int bsx_cartpole_mlp2_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                          float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return bsx_torso_entry<cartpole_host>(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
 }
 
-extern "C" int bsx_cartpole_mlp2_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, float* state,
-                                           int32_t* steps, bsx_linear_eval_t out, double* info) {
-  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
-}
-
-extern "C" int bsx_cartpole_mlp2_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, float* state,
-                                          int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+extern "C" int bsx_cartpole_mlp2_rollout(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
+                                         float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return bsx_torso_entry<cartpole_host>(cfg, call, mlp2, BSX_TORSO_GREEDY, 0.0, state, steps,
+                                        true, bsx_linear_eval_t{}, out, actions_out, info);
 }
 
 extern "C" int bsx_cartpole_mlp2_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, double inv_temperature,
-                                         float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps, true, bsx_linear_eval_t{}, out, actions_out, info);
+                                        float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return bsx_torso_entry<cartpole_host>(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps,
+                                        true, bsx_linear_eval_t{}, out, actions_out, info);
 }
 
-extern "C" int bsx_cartpole_mlp2_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2,
-                                                  double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
-                                                  double* info) {
-  return cartpole_torso(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps, false, out, bsx_timestep_t{}, nullptr, info);
+extern "C" int bsx_cartpole_mlp2_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp2_t* mlp2, double inv_temperature,
+                                                 float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return bsx_torso_entry<cartpole_host>(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature, state, steps,
+                                        false, out, bsx_timestep_t{}, nullptr, info);
 }
 
 // sample_linear / sample_mlp: the recording closed loop with actions drawn from softmax(logits * inv_temperature).
-template <class Policy>
-static int cartpole_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const Policy* policy, double inv_temperature, float* state,
-                           int32_t* steps, const bsx_timestep_t& out, int32_t* actions_out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  bsx_gumbel_args e;
-  cartpole_env::args* a = &e.t.fam.cartpole;
-  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
-  if (rc == 0)
-    rc = bsx_check_gumbel_call(call, policy, inv_temperature, state, steps, out, actions_out, info, cfg->time_frac, cfg->swingup ? 8 : 6);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (the kernel reads e.t.out)
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_gumbel_call(e, BSX_FAM_CARTPOLE, call, policy, inv_temperature, out, actions_out);
-}
-
-extern "C" int bsx_cartpole_linear_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
-                                           double inv_temperature, float* state, int32_t* steps, bsx_timestep_t out,
-                                           int32_t* actions_out, double* info) {
-  return cartpole_sample(cfg, call, linear, inv_temperature, state, steps, out, actions_out, info);
+extern "C" int bsx_cartpole_linear_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear, double inv_temperature,
+                                          float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return bsx_gumbel_entry<cartpole_host>(cfg, call, linear, inv_temperature, state, steps, out, actions_out, info);
 }
 
 extern "C" int bsx_cartpole_mlp_sample(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, double inv_temperature,
-                                        float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
-  return cartpole_sample(cfg, call, mlp, inv_temperature, state, steps, out, actions_out, info);
+                                       float* state, int32_t* steps, bsx_timestep_t out, int32_t* actions_out, double* info) {
+  return bsx_gumbel_entry<cartpole_host>(cfg, call, mlp, inv_temperature, state, steps, out, actions_out, info);
 }
 
 // evaluate_sampled_linear / evaluate_sampled_mlp: the sampled closed loop, writing only what the evaluation writes.
-template <class Policy>
-static int cartpole_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const Policy* policy, double inv_temperature,
-                                    float* state, int32_t* steps, const bsx_linear_eval_t& out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  bsx_drawn_returns_args e;
-  cartpole_env::args* a = &e.fam.cartpole;
-  int rc = (cfg->last_step < 1 || cfg->last_step >= (1 << 30)) ? BSX_ERANGE : cartpole_derive(cfg, a);
-  if (rc == 0) rc = bsx_check_drawn_returns_call(call, policy, inv_temperature, state, steps, out, info, cfg->time_frac);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  a->ctl = bsx_make_ctl(call); a->action = nullptr; a->state = state; a->steps = steps; a->out = bsx_timestep_t{};   // (no action column, no TimeStep)
-  a->info = info; a->obs_numel = cfg->swingup ? 8 : 6; a->cfg = *cfg;
-  return bsx_drawn_returns_call(e, BSX_FAM_CARTPOLE, call, policy, inv_temperature, out);
+extern "C" int bsx_cartpole_linear_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear, double inv_temperature,
+                                                   float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return bsx_drawn_returns_entry<cartpole_host>(cfg, call, linear, inv_temperature, state, steps, out, info);
 }
 
-extern "C" int bsx_cartpole_linear_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_linear_t* linear,
-                                                    double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
-                                                    double* info) {
-  return cartpole_sample_evaluate(cfg, call, linear, inv_temperature, state, steps, out, info);
-}
-
-extern "C" int bsx_cartpole_mlp_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp,
-                                                 double inv_temperature, float* state, int32_t* steps, bsx_linear_eval_t out,
-                                                 double* info) {
-  return cartpole_sample_evaluate(cfg, call, mlp, inv_temperature, state, steps, out, info);
+extern "C" int bsx_cartpole_mlp_sample_evaluate(const bsx_cartpole_t* cfg, const bsx_call_t* call, const bsx_mlp_t* mlp, double inv_temperature,
+                                                float* state, int32_t* steps, bsx_linear_eval_t out, double* info) {
+  return bsx_drawn_returns_entry<cartpole_host>(cfg, call, mlp, inv_temperature, state, steps, out, info);
 }
 
 extern "C" int bsx_group_set_cartpole(bsx_group_t* g, int32_t index, const bsx_cartpole_t* cfg, const bsx_call_t* call,

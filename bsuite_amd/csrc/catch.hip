@@ -9,6 +9,8 @@
 //   observe  bsx_hot_stream_kernel<catch_hot,2,256>: pure store stream over [B x rows*cols] f32.
 //            rows*cols = 50 is not a multiple of 4, so a 16-byte chunk may straddle two lanes'
 //            boards (one division per chunk, spill-over elements patched from lane l+1's state).
+// Host code: the family's host trait (catch_host: cfg check, fill, make), step, the group setter, and the eight fused
+// closed-loop entry points as one-statement delegations ("Host glue of the closed-loop calls").
 #include "bsx_embed_device.h"
 #include "bsx_pair_host.h"
 #include "bsx_tab_eval.h"
@@ -16,140 +18,95 @@
 #include "catch_fam.h"
 #include "pair_mixed.h"
 
-// The cfg's range check, the same for every entry point.
-static int catch_check_cfg(const bsx_catch_t* cfg) {
-  return (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) ? BSX_ERANGE : 0;
-}
-
-// The kernel argument struct of a checked call.
-static void catch_fill(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out,
-                       double* info, catch_fam::args* a) {
-  a->ctl = bsx_make_ctl(call);
-  a->action = action; a->state = state; a->out = out; a->info = info;
-  a->rows = cfg->rows; a->columns = cfg->columns;
-  a->tile_cells_magic = 0; a->_pad = 0;
-}
-
-static int catch_make(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
-                      bsx_timestep_t out, double* info, catch_fam::args* a) {
-  if (cfg == nullptr) return BSX_ENULL;
-  int rc = bsx_check_call(call, action, out, /*delta_ok=*/true, /*narrow_ok=*/true);
-  if (rc != 0) return rc;
-  if ((rc = catch_check_cfg(cfg)) != 0) return rc;
-  if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
-  catch_fill(cfg, call, action, state, out, info, a);
-  return 0;
-}
+// What differs between the grid families on the host: the trait of bsx_grid_closed_loop (bsx_host.h).
+namespace {                                 // (internal linkage: the library exports its C ABI and nothing else)
+struct catch_host {
+  typedef bsx_catch_t cfg_t;
+  typedef catch_fam fam;
+  typedef catch_hot hot_t;
+  static constexpr int32_t code = BSX_FAM_CATCH, actions = 3;
+  // The cfg's range check, the same for every entry point.
+  static int check_cfg(const cfg_t* cfg) {
+    return (cfg->rows < 2 || cfg->rows > 64 || cfg->columns < 1 || cfg->columns > 64) ? BSX_ERANGE : 0;
+  }
+  static int32_t states(const cfg_t* cfg) { return bsx_policy_states_catch(cfg->rows, cfg->columns); }
+  static int32_t cells(const cfg_t* cfg) { return cfg->rows * cfg->columns; }
+  static hot_t hot(const cfg_t* cfg) { return catch_hot{cfg->rows, cfg->columns}; }
+  // The kernel argument struct of a checked call.
+  static void fill(const cfg_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out, double* info,
+                   fam::args* a) {
+    a->ctl = bsx_make_ctl(call);
+    a->action = action; a->state = state; a->out = out; a->info = info;
+    a->rows = cfg->rows; a->columns = cfg->columns;
+    a->tile_cells_magic = 0; a->_pad = 0;
+  }
+  // Validates one call's arguments and fills the kernel argument struct (step, the groups and the recording closed loops).
+  static int make(const cfg_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out, double* info,
+                  fam::args* a) {
+    if (cfg == nullptr) return BSX_ENULL;
+    int rc = bsx_check_call(call, action, out, /*delta_ok=*/true, /*narrow_ok=*/true);
+    if (rc != 0) return rc;
+    if ((rc = check_cfg(cfg)) != 0) return rc;
+    if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
+    fill(cfg, call, action, state, out, info, a);
+    return 0;
+  }
+  template <class Union>
+  static fam::args* of(Union& u) { return &u.catch_; }
+};
+}  // namespace
 
 extern "C" int bsx_catch_step(const bsx_catch_t* cfg, const bsx_call_t* call, const int32_t* action,
                               int32_t* state, bsx_timestep_t out, double* info) {
   catch_fam::args a;
-  int rc = catch_make(cfg, call, action, state, out, info, &a);
+  int rc = catch_host::make(cfg, call, action, state, out, info, &a);
   if (rc != 0) return rc;
   if (call->n_lanes == 0) return 0;
   const uint32_t cells = (uint32_t)(cfg->rows * cfg->columns);
   return bsx_pair_call<catch_fam, catch_hot, 2>(a, call, action, state, out, cells, catch_hot{cfg->rows, cfg->columns});
 }
 
+// The eight fused closed-loop entry points: each body is stated once for both families, beside its kind's checks
+// (bsx_policy_rollout_entry, bsx_pair_host.h; bsx_tab_eval_entry; bsx_tab_softmax_entry; bsx_embed_entry), over the one
+// prologue of bsx_host.h.  A recording call is told from an evaluation by its output struct.
 extern "C" int bsx_catch_policy_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
                                         int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_policy_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  catch_fam::args a;
-  // (the action pointer of a policy rollout is never read: actions_out stands in for it in the common checks)
-  rc = catch_make(cfg, call, policy->actions_out, state, out, info, &a);
-  if (rc != 0) return rc;
-  a.action = nullptr;
-  return bsx_policy_rollout_call<catch_fam, catch_hot>(a, call, policy, 3u, out, catch_hot{cfg->rows, cfg->columns});
+  return bsx_policy_rollout_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
-extern "C" int bsx_catch_policy_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy, int32_t* state,
-                                          bsx_policy_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_policy_eval_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_tab_eval_args e;
-  catch_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &e.fam.catch_);          // (no action column, no TimeStep)
-  return bsx_tab_eval_call(e, BSX_FAM_CATCH, call, policy, 3u, out);
+extern "C" int bsx_catch_policy_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
+                                         int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_tab_eval_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_catch_policy_sample(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
                                        int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_tab_softmax_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), 3, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_tab_softmax_args s;
-  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_catch_policy_rollout)
-  rc = catch_make(cfg, call, policy->actions_out, state, out, info, &s.fam.catch_);
-  if (rc != 0) return rc;
-  s.fam.catch_.action = nullptr;
-  return bsx_tab_softmax_call(s, BSX_FAM_CATCH, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+  return bsx_tab_softmax_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_catch_policy_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
                                                 int32_t* state, bsx_policy_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_tab_softmax_eval_call(call, policy, bsx_policy_states_catch(cfg->rows, cfg->columns), 3, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_tab_softmax_args s;
-  catch_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.catch_);          // (no action column, no TimeStep)
-  return bsx_tab_softmax_call(s, BSX_FAM_CATCH, call, policy, false, nullptr, out);
+  return bsx_tab_softmax_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_catch_embedding_rollout(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
-                                        int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_call(call, policy, cfg->rows * cfg->columns, 3, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_catch_policy_rollout)
-  rc = catch_make(cfg, call, policy->actions_out, state, out, info, &s.fam.catch_);
-  if (rc != 0) return rc;
-  s.fam.catch_.action = nullptr;
-  return bsx_embed_call(s, BSX_FAM_CATCH, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+                                           int32_t* state, bsx_timestep_t out, double* info) {
+  return bsx_embed_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_catch_embedding_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
-                                         int32_t* state, bsx_policy_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_eval_call(call, policy, cfg->rows * cfg->columns, 3, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  catch_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.catch_);          // (no action column, no TimeStep)
-  return bsx_embed_call(s, BSX_FAM_CATCH, call, policy, false, nullptr, out);
+                                            int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_embed_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_catch_embedding_sample(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
-                                       int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_sample_call(call, policy, cfg->rows * cfg->columns, 3, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_catch_policy_rollout)
-  rc = catch_make(cfg, call, policy->actions_out, state, out, info, &s.fam.catch_);
-  if (rc != 0) return rc;
-  s.fam.catch_.action = nullptr;
-  return bsx_embed_sample_call(s, BSX_FAM_CATCH, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+                                          int32_t* state, bsx_timestep_t out, double* info) {
+  return bsx_embed_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
-extern "C" int bsx_catch_embedding_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call,
-                                                const bsx_policy_embedding_sample_t* policy, int32_t* state, bsx_policy_eval_t out,
-                                                double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = catch_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_sample_eval_call(call, policy, cfg->rows * cfg->columns, 3, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  catch_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.catch_);          // (no action column, no TimeStep)
-  return bsx_embed_sample_call(s, BSX_FAM_CATCH, call, policy, false, nullptr, out);
+extern "C" int bsx_catch_embedding_sample_evaluate(const bsx_catch_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                                   int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_embed_entry<catch_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catch_t* cfg, const bsx_call_t* call,
@@ -159,7 +116,7 @@ extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catc
   int rc;
   catch_fam::args a;
   if (bsx_is_mixed_pair_group(g)) {            // one segment of the mixed two-kernel group
-    rc = catch_make(cfg, call, action, state, out, info, &a);
+    rc = catch_host::make(cfg, call, action, state, out, info, &a);
     if (rc != 0) return rc;
     a.ctl.state_in = call->state_alt;            // pipelined sweeps: the advance reads the other column
     const uint32_t cells = (uint32_t)(cfg->rows * cfg->columns);
@@ -180,7 +137,7 @@ extern "C" int bsx_group_set_catch(bsx_group_t* g, int32_t index, const bsx_catc
   rc = bsx_group_check_set(g, BSX_FAM_CATCH, index, call, sizeof(catch_fam::args),
                            sizeof(bsx_stream_seg<catch_hot>), 0);
   if (rc != 0) return rc;
-  rc = catch_make(cfg, call, action, state, out, info, &a);
+  rc = catch_host::make(cfg, call, action, state, out, info, &a);
   if (rc != 0) return rc;
   g->launch = bsx_group_launch_pair<catch_fam, catch_hot, 2>;
   g->n_phases = 2;

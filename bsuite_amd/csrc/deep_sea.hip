@@ -15,6 +15,8 @@
 // Decoupling the two is what makes the store stream fast: single-kernel variants that advance
 // lanes, synchronise and then store (per-block 230 KB tiles, or flat 16 KiB runs with ping-pong
 // state) measured 5.1-5.5 TB/s against 6.2-6.4 TB/s for this pair (profiles/r01/ab_*.log).
+// Host code, below the kernels: the family's host trait (deep_sea_host: cfg check, fill, make), the step entries, the group
+// setter, and the eight fused closed-loop entry points as one-statement delegations ("Host glue of the closed-loop calls").
 #include "bsx_embed_device.h"
 #include "bsx_pair_host.h"
 #include "bsx_tab_eval.h"
@@ -257,40 +259,50 @@ __device__ __forceinline__ void deep_sea_hint_stream(float* __restrict__ obs, co
   }
 }
 
-// The cfg's range check, the same for every entry point.
-static int deep_sea_check_cfg(const bsx_deep_sea_t* cfg) {
-  return (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) ? BSX_ERANGE : 0;
-}
-
-// The kernel argument struct of a checked call.
-static void deep_sea_fill(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state,
-                          bsx_timestep_t out, double* info, deep_sea_fam::args* a) {
-  a->ctl = bsx_make_ctl(call);
-  a->action = action; a->state = state; a->out = out; a->info = info;
-  a->move_cost = cfg->move_cost; a->inv_size = cfg->inv_size;
-  a->size = cfg->size; a->deterministic = cfg->deterministic;
-  for (int w = 0; w < DS_MAP_WORDS; ++w) a->mapping_bits[w] = cfg->mapping_bits[w];
-}
-
-// Validates one call's arguments and fills the kernel argument struct (shared by step and group).
-static int deep_sea_make(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const int32_t* action,
-                         int32_t* state, bsx_timestep_t out, double* info, deep_sea_fam::args* a) {
-  if (cfg == nullptr) return BSX_ENULL;
-  int rc = bsx_check_call(call, action, out, /*delta_ok=*/true, /*narrow_ok=*/true);
-  if (rc != 0) return rc;
-  if ((rc = deep_sea_check_cfg(cfg)) != 0) return rc;
-  if (call->stream.mt_state != nullptr && !cfg->deterministic && call->stream.mt_gauss == nullptr)
-    return BSX_ENULL;                      // the stochastic variant draws randn: needs the gauss cache columns
-  if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
-  deep_sea_fill(cfg, call, action, state, out, info, a);
-  return 0;
-}
+// What differs between the grid families on the host: the trait of bsx_grid_closed_loop (bsx_host.h).
+namespace {                                 // (internal linkage: the library exports its C ABI and nothing else)
+struct deep_sea_host {
+  typedef bsx_deep_sea_t cfg_t;
+  typedef deep_sea_fam fam;
+  typedef deep_sea_hot hot_t;
+  static constexpr int32_t code = BSX_FAM_DEEP_SEA, actions = 2;
+  // The cfg's range check, the same for every entry point.
+  static int check_cfg(const cfg_t* cfg) { return (cfg->size < 1 || cfg->size > BSX_DEEP_SEA_MAX_SIZE) ? BSX_ERANGE : 0; }
+  static int32_t states(const cfg_t* cfg) { return bsx_policy_states_deep_sea(cfg->size); }
+  static int32_t cells(const cfg_t* cfg) { return cfg->size * cfg->size; }
+  static hot_t hot(const cfg_t* cfg) { return deep_sea_hot{cfg->size}; }
+  // The kernel argument struct of a checked call.
+  static void fill(const cfg_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out, double* info,
+                   fam::args* a) {
+    a->ctl = bsx_make_ctl(call);
+    a->action = action; a->state = state; a->out = out; a->info = info;
+    a->move_cost = cfg->move_cost; a->inv_size = cfg->inv_size;
+    a->size = cfg->size; a->deterministic = cfg->deterministic;
+    for (int w = 0; w < DS_MAP_WORDS; ++w) a->mapping_bits[w] = cfg->mapping_bits[w];
+  }
+  // Validates one call's arguments and fills the kernel argument struct (step, the groups and the recording closed loops).
+  static int make(const cfg_t* cfg, const bsx_call_t* call, const int32_t* action, int32_t* state, bsx_timestep_t out, double* info,
+                  fam::args* a) {
+    if (cfg == nullptr) return BSX_ENULL;
+    int rc = bsx_check_call(call, action, out, /*delta_ok=*/true, /*narrow_ok=*/true);
+    if (rc != 0) return rc;
+    if ((rc = check_cfg(cfg)) != 0) return rc;
+    if (call->stream.mt_state != nullptr && !cfg->deterministic && call->stream.mt_gauss == nullptr)
+      return BSX_ENULL;                      // the stochastic variant draws randn: needs the gauss cache columns
+    if (call->n_lanes > 0 && (state == nullptr || info == nullptr)) return BSX_ENULL;
+    fill(cfg, call, action, state, out, info, a);
+    return 0;
+  }
+  template <class Union>
+  static fam::args* of(Union& u) { return &u.deep_sea; }
+};
+}  // namespace
 
 extern "C" int bsx_deep_sea_step(const bsx_deep_sea_t* cfg, const bsx_call_t* call,
                                  const int32_t* action, int32_t* state, bsx_timestep_t out,
                                  double* info) {
   deep_sea_fam::args a;
-  int rc = deep_sea_make(cfg, call, action, state, out, info, &a);
+  int rc = deep_sea_host::make(cfg, call, action, state, out, info, &a);
   if (rc != 0) return rc;
   if (call->n_lanes == 0) return 0;
   const uint32_t cells = (uint32_t)(cfg->size * cfg->size);
@@ -322,7 +334,7 @@ extern "C" int bsx_deep_sea_step_hinted(const bsx_deep_sea_t* cfg, const bsx_cal
   // (the 16-byte alignment of the boards is one of this entry's modes: BSX_EMODE, ahead of the common checks' BSX_EALIGN)
   if ((reinterpret_cast<uintptr_t>(out.observation) & 15u) != 0) return BSX_EMODE;
   deep_sea_fam::args a;
-  int rc = deep_sea_make(cfg, call, action, state, out, info, &a);
+  int rc = deep_sea_host::make(cfg, call, action, state, out, info, &a);
   if (rc != 0) return rc;
   const uint32_t cells = (uint32_t)(cfg->size * cfg->size);
   if (!cfg->deterministic || !bsx_ctl_lean(a.ctl) || bsx_call_obs(call) != 0 || bsx_call_index(call) || call->obs_paint != nullptr ||
@@ -345,106 +357,47 @@ extern "C" int bsx_deep_sea_step_hinted(const bsx_deep_sea_t* cfg, const bsx_cal
   return bsx_launch_status();
 }
 
+// The eight fused closed-loop entry points: each body is stated once for both families, beside its kind's checks
+// (bsx_policy_rollout_entry, bsx_pair_host.h; bsx_tab_eval_entry; bsx_tab_softmax_entry; bsx_embed_entry), over the one
+// prologue of bsx_host.h.  A recording call is told from an evaluation by its output struct.
 extern "C" int bsx_deep_sea_policy_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
                                            int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_policy_call(call, policy, bsx_policy_states_deep_sea(cfg->size), state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  deep_sea_fam::args a;
-  // (the action pointer of a policy rollout is never read: actions_out stands in for it in the common checks)
-  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &a);
-  if (rc != 0) return rc;
-  a.action = nullptr;
-  return bsx_policy_rollout_call<deep_sea_fam, deep_sea_hot>(a, call, policy, 2u, out, deep_sea_hot{cfg->size});
+  return bsx_policy_rollout_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_deep_sea_policy_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_t* policy,
-                                             int32_t* state, bsx_policy_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_policy_eval_call(call, policy, bsx_policy_states_deep_sea(cfg->size), state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_tab_eval_args e;
-  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &e.fam.deep_sea);     // (no action column, no TimeStep)
-  return bsx_tab_eval_call(e, BSX_FAM_DEEP_SEA, call, policy, 2u, out);
+                                            int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_tab_eval_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_deep_sea_policy_sample(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
                                           int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_tab_softmax_call(call, policy, bsx_policy_states_deep_sea(cfg->size), 2, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_tab_softmax_args s;
-  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_deep_sea_policy_rollout)
-  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &s.fam.deep_sea);
-  if (rc != 0) return rc;
-  s.fam.deep_sea.action = nullptr;
-  return bsx_tab_softmax_call(s, BSX_FAM_DEEP_SEA, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+  return bsx_tab_softmax_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
-extern "C" int bsx_deep_sea_policy_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call,
-                                                   const bsx_policy_logits_t* policy, int32_t* state, bsx_policy_eval_t out,
-                                                   double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_tab_softmax_eval_call(call, policy, bsx_policy_states_deep_sea(cfg->size), 2, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_tab_softmax_args s;
-  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);     // (no action column, no TimeStep)
-  return bsx_tab_softmax_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
+extern "C" int bsx_deep_sea_policy_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_logits_t* policy,
+                                                   int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_tab_softmax_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_deep_sea_embedding_rollout(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
-                                        int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_deep_sea_policy_rollout)
-  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &s.fam.deep_sea);
-  if (rc != 0) return rc;
-  s.fam.deep_sea.action = nullptr;
-  return bsx_embed_call(s, BSX_FAM_DEEP_SEA, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+                                              int32_t* state, bsx_timestep_t out, double* info) {
+  return bsx_embed_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_deep_sea_embedding_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_t* policy,
-                                         int32_t* state, bsx_policy_eval_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_eval_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);          // (no action column, no TimeStep)
-  return bsx_embed_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
+                                               int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_embed_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_deep_sea_embedding_sample(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
-                                       int32_t* state, bsx_timestep_t out, double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_sample_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  // (no action column is read: actions_out stands in for it in the common checks, as in bsx_deep_sea_policy_rollout)
-  rc = deep_sea_make(cfg, call, policy->actions_out, state, out, info, &s.fam.deep_sea);
-  if (rc != 0) return rc;
-  s.fam.deep_sea.action = nullptr;
-  return bsx_embed_sample_call(s, BSX_FAM_DEEP_SEA, call, policy, true, reinterpret_cast<int32_t*>(out.observation), bsx_policy_eval_t{});
+                                             int32_t* state, bsx_timestep_t out, double* info) {
+  return bsx_embed_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
-extern "C" int bsx_deep_sea_embedding_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call,
-                                                const bsx_policy_embedding_sample_t* policy, int32_t* state, bsx_policy_eval_t out,
-                                                double* info) {
-  if (cfg == nullptr || call == nullptr || policy == nullptr) return BSX_ENULL;
-  int rc = deep_sea_check_cfg(cfg);
-  if (rc == 0) rc = bsx_check_embed_sample_eval_call(call, policy, cfg->size * cfg->size, 2, state, out, info);
-  if (rc != 0 || call->n_lanes == 0) return rc;
-  bsx_embed_args s;
-  deep_sea_fill(cfg, call, nullptr, state, bsx_timestep_t{}, info, &s.fam.deep_sea);          // (no action column, no TimeStep)
-  return bsx_embed_sample_call(s, BSX_FAM_DEEP_SEA, call, policy, false, nullptr, out);
+extern "C" int bsx_deep_sea_embedding_sample_evaluate(const bsx_deep_sea_t* cfg, const bsx_call_t* call, const bsx_policy_embedding_sample_t* policy,
+                                                      int32_t* state, bsx_policy_eval_t out, double* info) {
+  return bsx_embed_entry<deep_sea_host>(cfg, call, policy, state, out, info);
 }
 
 extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_deep_sea_t* cfg,
@@ -455,7 +408,7 @@ extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_d
   int rc;
   deep_sea_fam::args a;
   if (bsx_is_mixed_pair_group(g)) {            // one segment of the mixed two-kernel group
-    rc = deep_sea_make(cfg, call, action, state, out, info, &a);
+    rc = deep_sea_host::make(cfg, call, action, state, out, info, &a);
     if (rc != 0) return rc;
     a.ctl.state_in = call->state_alt;            // pipelined sweeps: the advance reads the other column
     const uint32_t cells = (uint32_t)(cfg->size * cfg->size);
@@ -468,7 +421,7 @@ extern "C" int bsx_group_set_deep_sea(bsx_group_t* g, int32_t index, const bsx_d
   rc = bsx_group_check_set(g, BSX_FAM_DEEP_SEA, index, call, sizeof(deep_sea_fam::args),
                            sizeof(bsx_stream_seg<deep_sea_hot>), 0);
   if (rc != 0) return rc;
-  rc = deep_sea_make(cfg, call, action, state, out, info, &a);
+  rc = deep_sea_host::make(cfg, call, action, state, out, info, &a);
   if (rc != 0) return rc;
   g->launch = bsx_group_launch_pair<deep_sea_fam, deep_sea_hot, 4>;
   g->n_phases = 2;

@@ -2,7 +2,7 @@
 // bsx_<family>_mlp_sample_evaluate): ONE kernel for cartpole, swing-up and mountain_car under a linear or a hidden-layer
 // softmax policy.  The family, its variant, whether the policy is shared and its kind are uniform switches, taken once per
 // launch; each of the twelve branches is bsx_drawn_returns_body (bsx_drawn_returns.h) instantiated for its case.  The entry
-// points are in cartpole.hip and mountain_car.hip.
+// points are in cartpole.hip and mountain_car.hip; their one body is bsx_drawn_returns_entry (bsx_drawn_returns.h).
 #include "bsx_drawn_returns.h"
 
 template <class Fam, int V>

@@ -3,7 +3,8 @@
 // kernel for deep_sea and catch, recording or returns only, greedy or drawn.  The family, the kind of call and the action
 // source are uniform switches, taken once per launch; each of the eight branches is a body of bsx_embed_device.h instantiated
 // for its family and its source.  The LDS holds the staged copy of a shared pair of matrices and both families' own staging
-// (deep_sea's action mapping; catch has none).  The entry points are in deep_sea.hip and catch.hip.
+// (deep_sea's action mapping; catch has none).  The entry points are in deep_sea.hip and catch.hip;
+// their bodies are the four bsx_embed_entry (bsx_embed_device.h).
 #include "bsx_embed_device.h"
 
 // Six waves per SIMD (80 vector registers) is the occupancy every branch has on its own (the largest, catch returns only,

@@ -1,7 +1,8 @@
 // gumbel.hip — sample_linear / sample_mlp (bsx_<family>_linear_sample, bsx_<family>_mlp_sample): ONE kernel for cartpole,
 // swing-up and mountain_car under a linear or a hidden-layer softmax policy.  The family, its variant, whether the policy is
 // shared and its kind are uniform switches, taken once per launch; each of the twelve branches is bsx_gumbel_body
-// (bsx_gumbel_device.h) instantiated for its case.  The entry points are in cartpole.hip and mountain_car.hip.
+// (bsx_gumbel_device.h) instantiated for its case.  The entry points are in cartpole.hip and mountain_car.hip;
+// their one body is bsx_gumbel_entry (bsx_gumbel_device.h).
 #include "bsx_gumbel_device.h"
 
 template <class Fam, int V>

@@ -1,7 +1,7 @@
 // linear.hip — evaluate_linear (bsx_cartpole_linear_evaluate, bsx_mountain_car_linear_evaluate): ONE kernel for cartpole,
 // swing-up and mountain_car.  The family, its variant and whether the weight matrix is shared are uniform switches, taken
 // once per launch; each branch is bsx_linear_score_body (bsx_linear_score.h) instantiated for its case.  The entry points
-// are in cartpole.hip and mountain_car.hip.
+// are in cartpole.hip and mountain_car.hip; their one body is bsx_linear_score_entry (bsx_linear_score.h).
 #include "bsx_linear_score.h"
 
 __global__ void __launch_bounds__(BSX_BLOCK) bsx_linear_score_kernel(const bsx_linear_score_args a) {

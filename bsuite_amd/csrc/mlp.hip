@@ -1,7 +1,7 @@
 // mlp.hip — evaluate_mlp (bsx_cartpole_mlp_evaluate, bsx_mountain_car_mlp_evaluate): ONE kernel for cartpole, swing-up and
 // mountain_car.  The family, its variant and whether the pair of matrices is shared are uniform switches, taken once per
 // launch; each branch is bsx_mlp_returns_body (bsx_mlp_returns.h) instantiated for its case.  The entry points are in
-// cartpole.hip and mountain_car.hip.
+// cartpole.hip and mountain_car.hip; their one body is bsx_mlp_returns_entry (bsx_mlp_returns.h).
 #include "bsx_mlp_returns.h"
 
 __global__ void __launch_bounds__(BSX_BLOCK) bsx_mlp_returns_kernel(const bsx_mlp_returns_args a) {

@@ -2,7 +2,7 @@
 // ONE kernel for deep_sea and catch, recording or returns only.  The family and the kind of call are uniform switches, taken
 // once per launch; each of the four branches is a body of bsx_tab_sample_device.h instantiated for its family.  The LDS holds
 // the shared table of logits and both families' own staging (deep_sea's action mapping; catch has none).  The entry points
-// are in deep_sea.hip and catch.hip.
+// are in deep_sea.hip and catch.hip; their bodies are the two bsx_tab_softmax_entry (bsx_tab_sample_device.h).
 #include "bsx_tab_sample_device.h"
 
 __global__ void __launch_bounds__(BSX_BLOCK) bsx_tab_softmax_kernel(const bsx_tab_softmax_args a) {

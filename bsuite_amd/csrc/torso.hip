@@ -6,7 +6,7 @@
 // twelve greedy ones with the mode's defaulted parameter left out, instruction for instruction what they were before the
 // drawn mode joined (the drawn bodies come first: with that order no greedy call measured slower).  A shared
 // triple is staged in dynamic LDS before the switch (its size depends on the call: the launch sizes the segment).  The
-// entry points are in cartpole.hip and mountain_car.hip.
+// entry points are in cartpole.hip and mountain_car.hip; their one body is bsx_torso_entry (bsx_torso.h).
 #include "bsx_torso.h"
 
 template <class Fam, int V>

@@ -1,7 +1,8 @@
 // trajectory.hip — rollout_linear / rollout_mlp (bsx_<family>_linear_rollout, bsx_<family>_mlp_rollout): ONE kernel for
 // cartpole, swing-up and mountain_car under a linear or a hidden-layer policy.  The family, its variant, whether the policy
 // is shared and its kind are uniform switches, taken once per launch; each of the twelve branches is bsx_trajectory_body
-// (bsx_trajectory.h) instantiated for its case.  The entry points are in cartpole.hip and mountain_car.hip.
+// (bsx_trajectory.h) instantiated for its case.  The entry points are in cartpole.hip and mountain_car.hip;
+// their one body is bsx_trajectory_entry (bsx_trajectory.h).
 #include "bsx_trajectory.h"
 
 template <class Fam, int V>

@@ -586,9 +586,11 @@ def test_the_kernel_body_draws_through_the_headers():
   stream_h = open(os.path.join(ROOT, 'include', 'bsx_stream.h')).read()
   assert '#define BSX_K(c) bsx_k_(c)' in stream_h
   # the entry points: the sampled check, then the greedy path's
+  # (bsx_torso_entry, stated once for both families in bsx_torso.h; the family's file delegates to it, twice in the drawn mode)
+  assert 'bsx_check_mlp2_sample_call(call, mlp2, inv_temperature,' in dev[dev.index('static inline int bsx_torso_entry('):]
   for fam in ('cartpole', 'mountain_car'):
     text = open(os.path.join(CSRC, fam + '.hip')).read()
-    assert 'bsx_check_mlp2_sample_call(call, mlp2, inv_temperature,' in text and text.count('BSX_TORSO_DRAWN, inv_temperature') == 2
+    assert text.count(f'bsx_torso_entry<{fam}_host>(cfg, call, mlp2, BSX_TORSO_DRAWN, inv_temperature') == 2
 
 
 # ------------------------------------------------------------------------------------------ the built library

@@ -190,11 +190,13 @@ def test_argument_checks_of_the_entry_points(fam, kind):
   for lanes in (slab, 1 << 31):
     assert run(call(n_lanes=lanes), policy(), info=None) == E.BSX_ENULL, lanes
     assert run(call(n_lanes=lanes), policy(), out=_native.LinearEvalPtrs(junk, junk, junk, 0)) == E.BSX_ENULL, lanes
-  hip = open(os.path.join(CSRC, fam + '.hip')).read()
-  body = hip[hip.index(f'static int {fam}_sample_evaluate('):]
+  # (the body of both families' entry points, stated once beside the kind's checks; the family's file delegates to it)
+  dev = open(os.path.join(CSRC, 'bsx_drawn_returns.h')).read()
+  body = dev[dev.index('static inline int bsx_drawn_returns_entry('):]
   body = body[:body.index('\n}\n')]
   assert 'bsx_check_drawn_returns_call(' in body and 'slab' not in body and 'bsx_check_trajectory' not in body
-  dev = open(os.path.join(CSRC, 'bsx_drawn_returns.h')).read()
+  hip = open(os.path.join(CSRC, fam + '.hip')).read()
+  assert hip.count(f'return bsx_drawn_returns_entry<{fam}_host>(cfg, call, ') == 2 and 'slab' not in hip
   assert 'bsx_check_trajectory' not in dev and '<< 32' not in dev
 
 
